@@ -14,12 +14,17 @@ time graph upload) is untimed — the rr graph is the fixed device model.
 
 N>1 is STRONG scaling: the same flow partitioned across GPUs.
 
+A plain run does only what the headline figure needs: setup, warmup, the
+timed flows, the optional output dump, the result line. --full is where
+any further measurement belongs (none at present).
+
 Launch (driver contract):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   # N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
   #        --master-addr 127.0.0.1 bench.py --gpus N ...
 """
 import argparse
+import gc
 import json
 import os
 import sys
@@ -29,6 +34,61 @@ from pathlib import Path
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 import numpy as np
+
+# --dump-outputs writes at most this much in all (the limit is 64 MB);
+# an array over its share is cut to a fixed, seeded sample of its entries
+DUMP_BUDGET_BYTES = 48 << 20
+
+
+def flow_outputs(flow):
+    """What a caller of the timed flow receives, as two sets of named
+    arrays: (exact, routed).
+
+    exact — the same bits in every run with the same arguments: the
+    placement (block coordinates, sub-tile slots, final bb and timing
+    costs) and the routing verdict [success, overused nodes].
+
+    routed — what the router produced: occupancy per rr node, routed
+    delay per sink, and [wirelength, critical path (s), iterations]. The
+    benched router lets the concurrent nets of a launch see each other's
+    congestion through unordered atomics, so these differ in detail from
+    run to run on identical inputs and are compared with a tolerance (see
+    docs/MEASUREMENTS.md for the measured spread). The CPU engines have
+    no device router: there only the summary is written."""
+    pl = flow["place"]
+    exact = {
+        "place_x": np.asarray(pl.x, dtype=np.float32),
+        "place_y": np.asarray(pl.y, dtype=np.float32),
+        "place_slot": np.asarray(pl.slot, dtype=np.float32),
+        "place_cost": np.array([pl.bb_cost, pl.td_cost], dtype=np.float64),
+        "route_verdict": np.array(
+            [float(flow["success"]), float(flow["route"]["overused"])],
+            dtype=np.float64),
+    }
+    routed = {
+        "route_summary": np.array(
+            [float(flow["wirelength"]), float(flow["cpd"]),
+             float(flow["route"]["iters"])], dtype=np.float64),
+    }
+    router = flow.get("router")
+    if router is not None:
+        routed["node_occ"] = router.t_occ.cpu().numpy().astype(np.float32)
+        routed["sink_delay"] = router.t_sink_delay.cpu().numpy().astype(
+            np.float32)
+    return exact, routed
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BUDGET_BYTES):
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    share = budget // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a).reshape(-1)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.random.default_rng(0).choice(a.size, keep, replace=False)
+            a = a[np.sort(idx)]
+        np.save(d / f"{name}.npy", a)
 
 
 def main():
@@ -45,7 +105,19 @@ def main():
     ap.add_argument("--max-iters", type=int, default=80)
     ap.add_argument("--inner-num", type=float, default=1.0)
     ap.add_argument("--verbose", action="store_true")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed flows, write the outputs of the "
+                         "last one: DIR/<name>.npy for those that are "
+                         "bit-identical from run to run (placement, its "
+                         "costs, routing verdict), DIR/routed/<name>.npy for "
+                         "the router's (occupancy, sink delays, summary), "
+                         "which vary slightly between runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that the headline "
+                         "figure does not need (none at present)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from parallel_eda_amd.arch.archdef import get_arch
@@ -105,35 +177,62 @@ def main():
                              max_route_iters=args.max_iters,
                              incremental=True, verbose=args.verbose)
 
+    # A flow's result carries its live GpuRouter (tens of GiB of search
+    # scratch at bitcoin scale), so only the most recent one is kept, and
+    # it is dropped — and its memory handed back to the device, which the
+    # router's scratch planner sizes itself against — before the next
+    # flow starts. Every flow therefore sees the same free memory.
+    last = None
+
+    # The release runs inside the timed region, so a step pays for it;
+    # release_s (printed with --verbose) says how much.
+    release_s = 0.0
+
+    def next_flow():
+        nonlocal last, release_s
+        t_rel = time.perf_counter()
+        last = None
+        if use_gpu:
+            gc.collect()
+            torch.cuda.empty_cache()
+        release_s += time.perf_counter() - t_rel
+        last = one_flow(args.seed)
+
     for w in range(args.warmup):
         t0 = time.perf_counter()
-        r = one_flow(args.seed)
+        next_flow()
         barrier_sync()
-        log(f"warmup {w}: {time.perf_counter()-t0:.1f}s success={r['success']}"
-            f" wl={r['wirelength']} cpd={r['cpd']*1e9:.2f}ns "
-            f"iters={r['route']['iters']} phases={r.get('phase_s')}")
+        log(f"warmup {w}: {time.perf_counter()-t0:.1f}s "
+            f"success={last['success']}"
+            f" wl={last['wirelength']} cpd={last['cpd']*1e9:.2f}ns "
+            f"iters={last['route']['iters']} phases={last.get('phase_s')}")
 
     barrier_sync()
     t0 = time.perf_counter()
-    flows = []
+    feasible = True
     for k in range(args.steps):
-        r = one_flow(args.seed)
-        flows.append(r)
-        log(f"step {k}: success={r['success']} wl={r['wirelength']} "
-            f"cpd={r['cpd']*1e9:.2f}ns iters={r['route']['iters']} "
-            f"phases={r.get('phase_s')} prof={r['route'].get('prof')} "
-            f"rprof={getattr(r.get('router'), 'prof', None)}")
+        next_flow()
+        feasible = feasible and bool(last["success"])
+        log(f"step {k}: success={last['success']} wl={last['wirelength']} "
+            f"cpd={last['cpd']*1e9:.2f}ns iters={last['route']['iters']} "
+            f"phases={last.get('phase_s')} prof={last['route'].get('prof')} "
+            f"rprof={getattr(last.get('router'), 'prof', None)}")
     barrier_sync()
     elapsed = time.perf_counter() - t0
+    log(f"release between flows: {release_s:.2f}s over "
+        f"{args.warmup + args.steps} flows")
     if dist is not None:
         from parallel_eda_amd.parallel.dist import allreduce_
         t = torch.tensor([elapsed], device=device if use_gpu else "cpu")
         allreduce_(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    feasible = all(f["success"] for f in flows)
     sec_per_flow = elapsed / args.steps
-    last = flows[-1]
+    if rank == 0 and args.dump_outputs:
+        exact, routed = flow_outputs(last)
+        dump_outputs(args.dump_outputs, exact, DUMP_BUDGET_BYTES // 2)
+        dump_outputs(Path(args.dump_outputs) / "routed", routed,
+                     DUMP_BUDGET_BYTES // 2)
     if rank == 0:
         out = {
             "metric": "place+route wall-clock to feasibility (s/flow; "

@@ -6,6 +6,8 @@ import subprocess
 import sys
 from pathlib import Path
 
+import pytest
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -38,3 +40,126 @@ def test_bench_single_cpu_fallback():
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     out = json.loads(lines[-1])
     assert out["n_gpus"] == 1 and out["value"] > 0
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path):
+    """An output over its share of the dump budget is cut to the same
+    seeded sample every time; small ones are written whole."""
+    import importlib.util
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(bench.DUMP_BUDGET_BYTES // 4 + 1000, dtype=np.float32)
+    small = np.arange(7, dtype=np.float64)
+    for sub in ("a", "b"):
+        bench.dump_outputs(tmp_path / sub, {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert np.array_equal(a, b)
+    assert a.nbytes <= bench.DUMP_BUDGET_BYTES // 2 < big.nbytes
+    assert np.all(np.diff(a) > 0) and a[-1] <= big[-1]
+    assert np.array_equal(np.load(tmp_path / "a" / "small.npy"), small)
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """Two runs with the same arguments dump bit-identical arrays in
+    DIR (the exact set)."""
+    import numpy as np
+    for sub in ("a", "b"):
+        r = subprocess.run(
+            [sys.executable, str(ROOT / "bench.py"), "--gpus", "1",
+             "--steps", "1", "--warmup", "0", "--config", "tseng",
+             "--fill", "0.3", "--dump-outputs", str(tmp_path / sub)],
+            capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+    files = sorted((tmp_path / "a").glob("*.npy"))
+    assert files
+    for f in files:
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+    # the CPU engines route serially, so here the routed set repeats too
+    f = Path("routed") / "route_summary.npy"
+    assert np.array_equal(np.load(tmp_path / "a" / f),
+                          np.load(tmp_path / "b" / f))
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed flow's arrays (float .npy,
+    within the size budget; the exact set in DIR, the routed set in
+    DIR/routed); --full is accepted and still ends in the same result
+    line; --steps sets the number of timed steps."""
+    import numpy as np
+    r = subprocess.run(
+        [sys.executable, str(ROOT / "bench.py"), "--gpus", "1",
+         "--steps", "3", "--warmup", "0", "--config", "tseng",
+         "--fill", "0.3", "--full", "--dump-outputs", str(tmp_path / "o")],
+        capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(
+        [l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["steps"] == 3 and out["feasible"]
+    assert abs(out["ms_per_step"] - out["value"] * 1000.0) <= 1.0
+    files = sorted((tmp_path / "o").glob("*.npy"))
+    names = {f.stem for f in files}
+    assert names == {"place_x", "place_y", "place_slot", "place_cost",
+                     "route_verdict"}
+    total = 0
+    for f in files:
+        a = np.load(f)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0
+        total += a.nbytes
+    assert total <= 64 * 10**6
+    routed = sorted((tmp_path / "o" / "routed").glob("*.npy"))
+    assert {f.stem for f in routed} == {"route_summary"}  # no device router
+    rs = np.load(routed[0])
+    assert rs.dtype == np.float64 and rs.nbytes + total <= 64 * 10**6
+    assert rs[0] == out["config"]["wirelength"]
+    assert abs(rs[1] * 1e9 - out["config"]["crit_path_ns"]) < 1e-3
+    assert rs[2] == out["config"]["route_iterations"]
+    v = np.load(tmp_path / "o" / "route_verdict.npy")
+    assert v[0] == 1.0 and v[1] == out["config"]["final_overused"] == 0
+    assert np.load(tmp_path / "o" / "place_cost.npy")[0] > 0
+    assert len(np.load(tmp_path / "o" / "place_x.npy")) == \
+        out["config"]["blocks"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_routed_gpu(tmp_path):
+    """On the GPU path the routed set holds the device router's own
+    arrays: occupancy per rr node and delay per routed sink, consistent
+    with the wirelength in the summary and in the result line. (Run-to-run
+    the routed set varies slightly, see docs/MEASUREMENTS.md; the exact
+    set is bit-identical, test_bench_dump_outputs_repeat.)"""
+    import numpy as np
+    from parallel_eda_amd import rrgraph
+    from parallel_eda_amd.arch.archdef import get_arch
+    r = subprocess.run(
+        [sys.executable, str(ROOT / "bench.py"), "--gpus", "1",
+         "--steps", "1", "--warmup", "0", "--config", "tseng",
+         "--fill", "0.3", "--dump-outputs", str(tmp_path / "o")],
+        capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(
+        [l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["dtype"] == "fp32" and out["feasible"]
+    d = tmp_path / "o"
+    assert {f.stem for f in d.glob("*.npy")} == {
+        "place_x", "place_y", "place_slot", "place_cost", "route_verdict"}
+    assert {f.stem for f in (d / "routed").glob("*.npy")} == {
+        "route_summary", "node_occ", "sink_delay"}
+    occ = np.load(d / "routed" / "node_occ.npy")
+    sd = np.load(d / "routed" / "sink_delay.npy")
+    rs = np.load(d / "routed" / "route_summary.npy")
+    assert occ.dtype == np.float32 and sd.dtype == np.float32
+    g = rrgraph.build_rr_graph(get_arch("tseng"))
+    assert len(occ) == g.num_nodes == out["config"]["rr_nodes"]
+    ty = np.asarray(g.type)
+    chan = (ty == 4) | (ty == 5)
+    seg = (np.asarray(g.xhigh).astype(np.int64) - np.asarray(g.xlow) +
+           np.asarray(g.yhigh) - np.asarray(g.ylow) + 1)
+    wl = int((occ[chan].astype(np.int64) * seg[chan]).sum())
+    assert wl == rs[0] == out["config"]["wirelength"]
+    assert abs(rs[1] * 1e9 - out["config"]["crit_path_ns"]) < 1e-3
+    assert np.isfinite(sd).all() and (sd > 0).all()
+    cap = np.asarray(g.capacity)
+    assert (occ >= 0).all() and (occ <= cap).all()
