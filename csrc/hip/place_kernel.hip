@@ -8,6 +8,9 @@
 // atomicMin (move-index priority => deterministic winner set); a second
 // kernel applies the conflict-free winners, whose deltas are exact and
 // additive (disjoint nets/locations => sequential-equivalent batch).
+// Two drivers run the same batch: pnr_place_batch (reset, propose,
+// resolve, apply: four launches, kept as the oracle) and pnr_place_run
+// (propose + commit with epoch-key claims, many batches per call).
 #include "pnr_hip.h"
 
 namespace pnrh {
@@ -543,6 +546,352 @@ __global__ void place_reset_claims_kernel(int32_t* net_claim, int32_t nn,
   }
 }
 
+// ===================================================================
+// Native run loop (pnr_place_run): two launches per batch, no reset, no
+// host round trip per batch. The four kernels above stay as they are
+// and serve as the oracle (GpuPlacer(legacy_batches=True)).
+//
+// Claims are 64-bit epoch keys taken with atomicMax:
+//   key = (uint64(batch) << 32) | (0xFFFFFFFF - move index)
+// A later batch beats every stale word, so the claim arrays are zeroed
+// once at construction (batch numbers start at 1) and never reset; within
+// a batch the lowest move index has the largest key, so the winner set is
+// the one atomicMin on the move index gives. "I hold this claim" is
+// claim == my key. The batch counter is 32 bits: it wraps after 4 G
+// batches and nothing guards against that.
+//
+// Control block ctrl[4] (device, zeroed by the host per run_batches call):
+//   [0] done     set by the stop rule; every kernel returns at once on it
+//   [1] n_exec   batches executed so far in this run_batches call
+//   [2] ticket   workgroup arrival counter of a checking commit launch
+struct RunDev {
+  int32_t* mv_from;                  // proposer's source tile x*gy+y
+  unsigned long long* net_claim;     // [num_nets] epoch keys
+  unsigned long long* loc_claim;     // [gx*gy] epoch keys
+  int32_t* ctrl;
+};
+
+__device__ __forceinline__ unsigned long long claim_key(uint32_t batch, int i) {
+  return ((unsigned long long)batch << 32) | (0xFFFFFFFFu - (uint32_t)i);
+}
+
+// place_propose_kernel with epoch-key claims, the done word and mv_from;
+// selection, deltas and Metropolis are the same code in the same order.
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_propose_run_kernel(PlaceDev p, MovesDev m, RunDev r,
+                                         float T, int rlim,
+                                         float timing_tradeoff,
+                                         float inv_bb_norm, float inv_td_norm,
+                                         uint32_t seed, uint32_t batch) {
+  if (r.ctrl[0]) return;
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
+  if (i >= m.n_moves) return;
+  const unsigned long long key = claim_key(batch, i);
+  int sel = -1, sx1 = -1, sy1 = -1, sslot = 0;
+  if (lane == 0) {
+    m.mv_flags[i] = 0;
+    sel = propose_select_impl(p, rlim, seed, batch, i, sx1, sy1, sslot);
+  }
+  sel = __shfl(sel, 0);
+  if (sel < 0) return;
+  const int x1 = __shfl(sx1, 0);
+  const int y1 = __shfl(sy1, 0);
+  const int slot1 = __shfl(sslot, 0);
+  const int32_t blk = sel;
+  const int x0 = p.bx[blk], y0 = p.by[blk];
+  const int mid = p.macro_of ? p.macro_of[blk] : -1;
+  if (mid >= 0) {
+    const int ddx = x1 - x0, ddy = y1 - y0;
+    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
+    if (mm1 - mm0 > 16) return;
+    int ok = 0;
+    if (lane == 0) {
+      ok = 1;
+      for (int32_t j = mm0; j < mm1 && ok; ++j) {
+        int32_t b = p.macro_blk[j];
+        int sx = p.bx[b], sy = p.by[b];
+        int tx = sx + ddx, ty = sy + ddy;
+        if (p.fixed && p.fixed[b]) ok = 0;
+        else if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) ok = 0;
+        else if (p.rx0 >= 0 && (tx < p.rx0 || tx > p.rx1 ||
+                                sx < p.rx0 || sx > p.rx1)) ok = 0;
+        else if (p.tile_btype
+                     ? (p.tile_btype[tx * p.gy + ty] != p.blk_type[b])
+                     : (is_io_loc(p, tx, ty) != (p.blk_type[b] == 0))) ok = 0;
+        else if (cap_at(p, tx, ty) != 1) ok = 0;
+        else {
+          int32_t occ = p.grid[((int64_t)tx * p.gy + ty) * p.cap];
+          if (occ >= 0 && p.macro_of[occ] != mid) ok = 0;
+        }
+      }
+      if (ok) atomicAdd(&m.counters[0], 1);
+    }
+    ok = __shfl(ok, 0);
+    if (!ok) return;
+    float dbb = 0.0f, dtd = 0.0f;
+    for (int32_t j = mm0; j < mm1; ++j) {
+      int32_t b = p.macro_blk[j];
+      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
+           k += 64) {
+        int32_t n = p.blk_nets[k];
+        bool dup = false;
+        for (int32_t j2 = mm0; j2 < j && !dup; ++j2)
+          dup = blk_has_net(p, p.macro_blk[j2], n);
+        if (dup) continue;
+        dbb += net_bb_cost_macro(p, n, mid, ddx, ddy) - p.net_cost[n];
+        if (timing_tradeoff > 0.0f)
+          dtd += net_td_cost_macro(p, n, mid, ddx, ddy) - p.net_tcost[n];
+      }
+    }
+    dbb = wave_sum_f32(dbb);
+    dtd = wave_sum_f32(dtd);
+    float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
+                  timing_tradeoff * dtd * inv_td_norm;
+    bool accept;
+    if (delta <= 0.0f) accept = true;
+    else if (T <= 0.0f) accept = false;
+    else {
+      float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
+                (1.0f / 16777216.0f);
+      accept = u < __expf(-delta / T);
+    }
+    if (!accept) return;
+    if (lane == 0) {
+      atomicAdd(&m.counters[1], 1);
+      m.mv_blk[i] = blk;
+      m.mv_to[i] = ((ddx + 4096) << 13) | (ddy + 4096);
+      m.mv_other[i] = -2 - mid;
+      m.mv_dbb[i] = dbb;
+      m.mv_dtd[i] = dtd;
+      m.mv_flags[i] = 1;
+      r.mv_from[i] = x0 * p.gy + y0;
+    }
+    for (int32_t j = mm0; j < mm1; ++j) {
+      int32_t b = p.macro_blk[j];
+      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
+           k += 64)
+        atomicMax(&r.net_claim[p.blk_nets[k]], key);
+    }
+    for (int32_t j = mm0 + lane; j < mm1; j += 64) {
+      int32_t b = p.macro_blk[j];
+      atomicMax(&r.loc_claim[p.bx[b] * p.gy + p.by[b]], key);
+      atomicMax(&r.loc_claim[(p.bx[b] + ddx) * p.gy + p.by[b] + ddy], key);
+    }
+    return;
+  }
+  int32_t other = p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1];
+  if (other == blk) return;
+  if (other >= 0 && p.fixed && p.fixed[other]) return;
+  if (other >= 0 && p.macro_of && p.macro_of[other] >= 0)
+    return;   // never swap a chain member out from under its macro
+  if (lane == 0) atomicAdd(&m.counters[0], 1);  // valid proposals only
+  float dbb = 0.0f, dtd = 0.0f;
+  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
+  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
+       k += 64) {
+    int32_t n = p.blk_nets[k];
+    dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
+    if (timing_tradeoff > 0.0f)
+      dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
+  }
+  if (other >= 0) {
+    for (int32_t k = p.blk_net_ptr[other] + lane;
+         k < p.blk_net_ptr[other + 1]; k += 64) {
+      int32_t n = p.blk_nets[k];
+      if (blk_has_net(p, blk, n)) continue;
+      dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
+      if (timing_tradeoff > 0.0f)
+        dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
+    }
+  }
+  dbb = wave_sum_f32(dbb);
+  dtd = wave_sum_f32(dtd);
+  float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
+                timing_tradeoff * dtd * inv_td_norm;
+  bool accept;
+  if (delta <= 0.0f) accept = true;
+  else if (T <= 0.0f) accept = false;
+  else {
+    float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
+              (1.0f / 16777216.0f);
+    accept = u < __expf(-delta / T);
+  }
+  if (!accept) return;
+  if (lane == 0) {
+    atomicAdd(&m.counters[1], 1);
+    m.mv_blk[i] = blk;
+    m.mv_to[i] = ((x1 * p.gy + y1) * p.cap + slot1);
+    m.mv_other[i] = other;
+    m.mv_dbb[i] = dbb;
+    m.mv_dtd[i] = dtd;
+    m.mv_flags[i] = 1;
+    r.mv_from[i] = x0 * p.gy + y0;
+    atomicMax(&r.loc_claim[x0 * p.gy + y0], key);
+    atomicMax(&r.loc_claim[x1 * p.gy + y1], key);
+  }
+  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
+       k += 64)
+    atomicMax(&r.net_claim[p.blk_nets[k]], key);
+  if (other >= 0)
+    for (int32_t k = p.blk_net_ptr[other] + lane;
+         k < p.blk_net_ptr[other + 1]; k += 64)
+      atomicMax(&r.net_claim[p.blk_nets[k]], key);
+}
+
+// Resolve and apply of one move by its wave: the verdict of
+// place_resolve_kernel, then at once the body of place_apply_kernel for a
+// winner. Why no wave depends on what another writes in the same launch is
+// argued in docs/KERNELS.md (placer section); in short, the verdict of a
+// single move reads only claims and its own mv_* words (source tile from
+// mv_from, not bx/by), a winner's apply reads positions of blocks on nets
+// and tiles that it alone holds, and a macro proposal that can read a
+// position torn by the winning proposal of the same chain holds none of
+// that chain's source tiles and loses whatever it reads.
+__device__ void commit_move(const PlaceDev& p, const MovesDev& m,
+                            const RunDev& r, float timing_tradeoff,
+                            double* cost_acc, uint32_t batch) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
+  if (i >= m.n_moves || m.mv_flags[i] != 1) return;
+  const unsigned long long key = claim_key(batch, i);
+  int32_t blk = m.mv_blk[i];
+  int32_t other = m.mv_other[i];
+  int32_t to = m.mv_to[i];
+  bool bad = false;
+  if (other <= -2) {
+    const int mid = -2 - other;
+    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
+    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
+    for (int32_t j = mm0 + lane; j < mm1; j += 64) {
+      int32_t b = p.macro_blk[j];
+      int sx = p.bx[b], sy = p.by[b];
+      int tx = sx + ddx, ty = sy + ddy;
+      // a torn read (see above) may point off the grid; such a wave has
+      // lost already, the test only keeps the claim load in bounds
+      if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) bad = true;
+      else if (r.loc_claim[sx * p.gy + sy] != key ||
+               r.loc_claim[tx * p.gy + ty] != key) bad = true;
+    }
+    for (int32_t j = mm0; j < mm1; ++j) {
+      int32_t b = p.macro_blk[j];
+      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
+           k += 64)
+        if (r.net_claim[p.blk_nets[k]] != key) bad = true;
+    }
+  } else {
+    int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
+    if (lane == 0 && (r.loc_claim[r.mv_from[i]] != key ||
+                      r.loc_claim[x1 * p.gy + y1] != key)) bad = true;
+    for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
+         k += 64)
+      if (r.net_claim[p.blk_nets[k]] != key) bad = true;
+    if (other >= 0)
+      for (int32_t k = p.blk_net_ptr[other] + lane;
+           k < p.blk_net_ptr[other + 1]; k += 64)
+        if (r.net_claim[p.blk_nets[k]] != key) bad = true;
+  }
+  const bool win = !__any(bad);
+  if (lane == 0) {
+    if (!win) { m.mv_flags[i] = 0; atomicAdd(&m.counters[3], 1); }
+    else { m.mv_flags[i] = 2; atomicAdd(&m.counters[2], 1); }
+  }
+  if (!win) return;
+  // ---- apply (net costs first on the pre-move positions, then lane 0
+  // commits grid and positions; same order as place_apply_kernel) ----
+  if (other <= -2) {
+    const int mid = -2 - other;
+    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
+    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
+    for (int32_t j = mm0; j < mm1; ++j) {
+      int32_t b = p.macro_blk[j];
+      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
+           k += 64) {
+        int32_t n = p.blk_nets[k];
+        p.net_cost[n] = net_bb_cost_macro(p, n, mid, ddx, ddy);
+        if (timing_tradeoff > 0.0f)
+          p.net_tcost[n] = net_td_cost_macro(p, n, mid, ddx, ddy);
+      }
+    }
+    if (lane == 0) {
+      for (int32_t j = mm0; j < mm1; ++j) {
+        int32_t b = p.macro_blk[j];
+        p.grid[((int64_t)p.bx[b] * p.gy + p.by[b]) * p.cap + p.bslot[b]] = -1;
+      }
+      for (int32_t j = mm0; j < mm1; ++j) {
+        int32_t b = p.macro_blk[j];
+        int tx = p.bx[b] + ddx, ty = p.by[b] + ddy;
+        p.grid[((int64_t)tx * p.gy + ty) * p.cap] = b;
+        p.bx[b] = tx; p.by[b] = ty; p.bslot[b] = 0;
+      }
+      unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
+      unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
+    }
+    return;
+  }
+  int slot1 = to % p.cap;
+  int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
+  int x0 = p.bx[blk], y0 = p.by[blk], s0 = p.bslot[blk];
+  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
+  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
+       k += 64) {
+    int32_t n = p.blk_nets[k];
+    p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
+    if (timing_tradeoff > 0.0f)
+      p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
+  }
+  if (other >= 0)
+    for (int32_t k = p.blk_net_ptr[other] + lane;
+         k < p.blk_net_ptr[other + 1]; k += 64) {
+      int32_t n = p.blk_nets[k];
+      p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
+      if (timing_tradeoff > 0.0f)
+        p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
+    }
+  if (lane == 0) {
+    p.grid[((int64_t)x0 * p.gy + y0) * p.cap + s0] = other >= 0 ? other : -1;
+    p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1] = blk;
+    p.bx[blk] = x1; p.by[blk] = y1; p.bslot[blk] = slot1;
+    if (other >= 0) { p.bx[other] = x0; p.by[other] = y0; p.bslot[other] = s0; }
+    unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
+    unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
+  }
+}
+
+// check != 0 on the 4th, 8th, ... batch of a run_batches call: the last
+// workgroup to arrive (ticket == gridDim.x - 1) evaluates the stop rule.
+// Nothing waits: every workgroup adds its ticket and leaves.
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_commit_kernel(PlaceDev p, MovesDev m, RunDev r,
+                                    float timing_tradeoff, double* cost_acc,
+                                    uint32_t batch, int check,
+                                    int32_t target_moves) {
+  if (r.ctrl[0]) return;
+  commit_move(p, m, r, timing_tradeoff, cost_acc, batch);
+  if (!check) return;
+  // this wave's counter atomics have been performed ...
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  // ... and are ordered before the ticket
+  __threadfence();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  int ticket = __hip_atomic_fetch_add(&r.ctrl[2], 1, __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_AGENT);
+  if (ticket != (int)gridDim.x - 1) return;
+  __threadfence();
+  int att = __hip_atomic_load(&m.counters[0], __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+  int acc = __hip_atomic_load(&m.counters[1], __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+  int win = __hip_atomic_load(&m.counters[2], __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+  r.ctrl[1] += 4;
+  if (win + (att - acc) >= target_moves) r.ctrl[0] = 1;
+  __hip_atomic_store(&r.ctrl[2], 0, __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // full net-cost refresh (init + periodic drift resync).
 // Host must zero out[0..1] before the launch.
 __global__ void place_refresh_costs_kernel(PlaceDev p, float timing_tradeoff,
@@ -589,6 +938,11 @@ struct PlaceLaunchArgs {
   float inv_bb_norm, inv_td_norm;
   uint32_t seed, batch;
   double* cost_acc;
+  // pnr_place_run only (see RunDev); net_claim/loc_claim above are the
+  // int32 words of pnr_place_batch
+  int32_t* mv_from;
+  unsigned long long* net_claim64; unsigned long long* loc_claim64;
+  int32_t* run_ctrl;
 };
 
 static void unpack(const PlaceLaunchArgs* a, PlaceDev& p, MovesDev& m) {
@@ -632,6 +986,38 @@ int pnr_place_batch(const PlaceLaunchArgs* a, void* stream) {
                      0, s, p, m);
   hipLaunchKernelGGL(place_apply_kernel, dim3(mg), dim3(64 * PROP_WAVES),
                      0, s, p, m, a->timing_tradeoff, a->cost_acc);
+  return (int)hipGetLastError();
+}
+
+// Enqueue n_batches batches (numbers first_batch, first_batch + 1, ...)
+// back to back, two launches each, with no host synchronisation. The
+// stop rule of GpuPlacer.run_batches runs on the device after every 4th
+// batch; once it fires the remaining launches return at once. n_batches
+// must be a multiple of 4 so that the 4th, 8th, ... batch of the
+// run_batches call is also the 4th, 8th, ... of each chunk.
+int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
+                  int32_t target_moves, int32_t n_batches, void* stream) {
+  if (n_batches < 0 || (n_batches & 3) || first_batch == 0 ||
+      !a->mv_from || !a->net_claim64 || !a->loc_claim64 || !a->run_ctrl)
+    return (int)hipErrorInvalidValue;
+  PlaceDev p; MovesDev m;
+  unpack(a, p, m);
+  RunDev r;
+  r.mv_from = a->mv_from;
+  r.net_claim = a->net_claim64; r.loc_claim = a->loc_claim64;
+  r.ctrl = a->run_ctrl;
+  hipStream_t s = (hipStream_t)stream;
+  int mg = (m.n_moves + PROP_WAVES - 1) / PROP_WAVES;
+  for (int32_t k = 0; k < n_batches; ++k) {
+    const uint32_t batch = first_batch + (uint32_t)k;
+    hipLaunchKernelGGL(place_propose_run_kernel, dim3(mg),
+                       dim3(64 * PROP_WAVES), 0, s, p, m, r, a->T, a->rlim,
+                       a->timing_tradeoff, a->inv_bb_norm, a->inv_td_norm,
+                       a->seed, batch);
+    hipLaunchKernelGGL(place_commit_kernel, dim3(mg), dim3(64 * PROP_WAVES),
+                       0, s, p, m, r, a->timing_tradeoff, a->cost_acc, batch,
+                       (int)(((k + 1) & 3) == 0), target_moves);
+  }
   return (int)hipGetLastError();
 }
 

@@ -1,12 +1,16 @@
 """GPU SA placer driver (host side of csrc/hip/place_kernel.hip).
 
 Shares the adaptive outer schedule with the CPU oracle (placer.py) but runs
-move batches as propose/resolve/apply kernel triples. Batched moves with
+move batches as propose + commit (resolve and apply) kernel pairs, enqueued
+in chunks by the native run loop pnr_place_run. Batched moves with
 exclusive net+tile claims are sequential-equivalent (disjoint winners,
 exact deltas), so the anneal semantics match the reference's try_swap loop
-at a per-batch granularity.
+at a per-batch granularity. The earlier driver, one four-kernel
+pnr_place_batch call per batch, stays selectable (legacy_batches=True) as
+the oracle the run loop is tested against.
 """
 import ctypes as ct
+import math
 
 import numpy as np
 
@@ -42,7 +46,17 @@ class PlaceLaunchArgs(ct.Structure):
         ("inv_bb_norm", ct.c_float), ("inv_td_norm", ct.c_float),
         ("seed", ct.c_uint32), ("batch", ct.c_uint32),
         ("cost_acc", ct.c_void_p),
+        # pnr_place_run only: source tiles, 64-bit epoch claims, control block
+        ("mv_from", ct.c_void_p),
+        ("net_claim64", ct.c_void_p), ("loc_claim64", ct.c_void_p),
+        ("run_ctrl", ct.c_void_p),
     ]
+
+
+# Batches enqueued per pnr_place_run call (a multiple of 4, the stop rule's
+# period). Between chunks the host reads the control block once; past the
+# stop point the rest of a chunk costs empty launches only.
+RUN_CHUNK_BATCHES = 32
 
 
 def _lib():
@@ -50,6 +64,9 @@ def _lib():
     if not hasattr(lib, "_place_ready"):
         lib.pnr_place_batch.restype = ct.c_int
         lib.pnr_place_batch.argtypes = [ct.POINTER(PlaceLaunchArgs), ct.c_void_p]
+        lib.pnr_place_run.restype = ct.c_int
+        lib.pnr_place_run.argtypes = [ct.POINTER(PlaceLaunchArgs), ct.c_uint32,
+                                      ct.c_int32, ct.c_int32, ct.c_void_p]
         lib.pnr_place_refresh.restype = ct.c_int
         lib.pnr_place_refresh.argtypes = [ct.POINTER(PlaceLaunchArgs), ct.c_void_p]
         lib.pnr_place_args_sizeof.restype = ct.c_int64
@@ -66,9 +83,12 @@ def ptr(t):
 class GpuPlacer:
     def __init__(self, netlist, arch: ArchDef, seed=7, timing=False,
                  device="cuda:0", n_moves=None, fixed=None,
-                 delay_matrix="analytic", macros=None):
+                 delay_matrix="analytic", macros=None, legacy_batches=False):
         import torch
         self.torch = torch
+        # True: one pnr_place_batch call per batch with a host check every
+        # fourth (the oracle for the native run loop, pnr_place_run)
+        self.legacy_batches = legacy_batches
         self.device = device
         self.arch = arch
         self.nl = netlist
@@ -86,10 +106,9 @@ class GpuPlacer:
         net_blk_ptr = np.r_[0, np.cumsum(counts)].astype(np.int32)
         net_blks = np.empty(net_blk_ptr[-1], dtype=np.int32)
         net_blks[net_blk_ptr[:-1]] = netlist.net_driver
-        sidx = np.concatenate([
-            np.arange(net_blk_ptr[i] + 1, net_blk_ptr[i + 1])
-            for i in range(nn)]) if nn else np.zeros(0, dtype=np.int64)
-        net_blks[sidx] = netlist.net_sinks
+        is_sink = np.ones(len(net_blks), dtype=bool)
+        is_sink[net_blk_ptr[:-1]] = False
+        net_blks[is_sink] = netlist.net_sinks
         # block -> nets CSR (deduped per block), vectorized: sort (block,
         # net) membership pairs and drop duplicates within a block
         net_of_member = np.repeat(np.arange(nn, dtype=np.int64),
@@ -101,7 +120,7 @@ class GpuPlacer:
         blk_net_ptr = np.zeros(nb + 1, dtype=np.int32)
         np.add.at(blk_net_ptr, mb + 1, 1)
         blk_net_ptr = np.cumsum(blk_net_ptr, dtype=np.int64).astype(np.int32)
-        q = np.array([_cross_count(int(c)) for c in counts], dtype=np.float32)
+        q = _cross_count_vec(counts).astype(np.float32)
 
         def up(a, dtype=None):
             t = torch.from_numpy(np.ascontiguousarray(a))
@@ -190,9 +209,25 @@ class GpuPlacer:
         self.t_mv_dbb = torch.zeros(nm, dtype=torch.float32, device=device)
         self.t_mv_dtd = torch.zeros(nm, dtype=torch.float32, device=device)
         self.t_mv_flags = torch.zeros(nm, dtype=torch.uint8, device=device)
-        self.t_net_claim = torch.zeros(nn, dtype=torch.int32, device=device)
-        self.t_loc_claim = torch.zeros(gx * gy, dtype=torch.int32, device=device)
-        self.t_counters = torch.zeros(4, dtype=torch.int32, device=device)
+        self.t_net_claim = self.t_loc_claim = None
+        self.t_net_claim64 = self.t_loc_claim64 = None
+        if legacy_batches:
+            self.t_net_claim = torch.zeros(nn, dtype=torch.int32, device=device)
+            self.t_loc_claim = torch.zeros(gx * gy, dtype=torch.int32,
+                                           device=device)
+        else:
+            # epoch-key claims: zeroed here once, never reset (batch
+            # numbers start at 1, so every key beats the zero word)
+            self.t_net_claim64 = torch.zeros(nn, dtype=torch.int64,
+                                             device=device)
+            self.t_loc_claim64 = torch.zeros(gx * gy, dtype=torch.int64,
+                                             device=device)
+        self.t_mv_from = torch.zeros(nm, dtype=torch.int32, device=device)
+        # counters [4] and the run loop's control block [4] (done, batches
+        # executed, ticket, unused) share one buffer: one copy reads both
+        self.t_run_state = torch.zeros(8, dtype=torch.int32, device=device)
+        self.t_counters = self.t_run_state[:4]
+        self.t_run_ctrl = self.t_run_state[4:]
         self.t_cost_acc = torch.zeros(2, dtype=torch.float64, device=device)
 
         self.lib = _lib()
@@ -343,7 +378,16 @@ class GpuPlacer:
         a.mv_blk = ptr(self.t_mv_blk); a.mv_to = ptr(self.t_mv_to)
         a.mv_other = ptr(self.t_mv_other); a.mv_dbb = ptr(self.t_mv_dbb)
         a.mv_dtd = ptr(self.t_mv_dtd); a.mv_flags = ptr(self.t_mv_flags)
-        a.net_claim = ptr(self.t_net_claim); a.loc_claim = ptr(self.t_loc_claim)
+        if self.legacy_batches:
+            a.net_claim = ptr(self.t_net_claim)
+            a.loc_claim = ptr(self.t_loc_claim)
+            a.net_claim64 = a.loc_claim64 = None
+        else:
+            a.net_claim = a.loc_claim = None
+            a.net_claim64 = ptr(self.t_net_claim64)
+            a.loc_claim64 = ptr(self.t_loc_claim64)
+        a.mv_from = ptr(self.t_mv_from)
+        a.run_ctrl = ptr(self.t_run_ctrl)
         a.counters = ptr(self.t_counters); a.n_moves = self.n_moves
         a.T = T; a.rlim = max(1, int(rlim)); a.timing_tradeoff = tt
         a.inv_bb_norm = inv_bb; a.inv_td_norm = inv_td
@@ -369,7 +413,41 @@ class GpuPlacer:
         """Launch move batches until ~target_moves moves have been DECIDED
         (applied winners + Metropolis rejects; claim-conflict losers don't
         count — they were never decided). Returns (success_rate, attempts).
-        Mirrors the serial placer's move_lim semantics under batching."""
+        Mirrors the serial placer's move_lim semantics under batching.
+
+        The stop rule is evaluated after every 4th batch: by the device in
+        the native run loop, by the host in the legacy loop. Both run the
+        same batches and advance batch_counter by the batches executed."""
+        if self.legacy_batches:
+            return self._run_batches_legacy(T, rlim, target_moves, tt,
+                                            bb_norm, td_norm, max_batches)
+        self.t_run_state.zero_()    # counters and control block
+        a = self._args(T=T, rlim=rlim, tt=tt,
+                       inv_bb=1.0 / bb_norm, inv_td=1.0 / td_norm)
+        target = int(min(max(math.ceil(target_moves), -0x7FFFFFFF),
+                         0x7FFFFFFF))
+        cap = 4 * ((max_batches + 3) // 4)   # the legacy loop runs in fours
+        first = self.batch_counter + 1
+        enq = 0
+        att = acc = executed = 0
+        while enq < cap:
+            n = min(RUN_CHUNK_BATCHES, cap - enq)
+            rc = self.lib.pnr_place_run(ct.byref(a), first + enq, target, n,
+                                        self._stream())
+            hip_api.check(rc, "place_run")
+            enq += n
+            # one small device-to-host copy per chunk (it synchronises)
+            st = self.t_run_state.cpu().numpy()
+            att, acc = int(st[0]), int(st[1])
+            done, executed = int(st[4]), int(st[5])
+            if done:
+                break
+        self.batch_counter += executed
+        srate = acc / max(1, att)
+        return srate, att
+
+    def _run_batches_legacy(self, T, rlim, target_moves, tt, bb_norm, td_norm,
+                            max_batches=256):
         self.t_counters.zero_()
         batches = 0
         win = att = acc = 0
@@ -416,19 +494,20 @@ class GpuPlacer:
         nl = self.nl
         tb = (self.arch.tile_btype_grid().reshape(self.gx, self.gy)
               if self.arch.is_heterogeneous() else None)
-        for b in range(nl.num_blocks):
-            x, y = bx[b], by[b]
-            if tb is not None:
-                if tb[x, y] != nl.block_type[b]:
-                    return False, f"block {b} type/loc mismatch"
-            else:
-                io = nl.block_type[b] == 0
-                on_io = (x == 0 or x == self.gx - 1 or y == 0 or
-                         y == self.gy - 1)
-                if io != on_io:
-                    return False, f"block {b} type/loc mismatch"
-            if grid[x, y, bslot[b]] != b:
-                return False, f"grid inconsistent at block {b}"
+        btype = np.asarray(nl.block_type)
+        if tb is not None:
+            bad_type = tb[bx, by] != btype
+        else:
+            on_io = ((bx == 0) | (bx == self.gx - 1) | (by == 0) |
+                     (by == self.gy - 1))
+            bad_type = (btype == 0) != on_io
+        bad_grid = grid[bx, by, bslot] != np.arange(nl.num_blocks)
+        bad = bad_type | bad_grid
+        if bad.any():
+            b = int(np.argmax(bad))     # first offending block
+            if bad_type[b]:
+                return False, f"block {b} type/loc mismatch"
+            return False, f"grid inconsistent at block {b}"
         occ = (grid >= 0).sum()
         if occ != nl.num_blocks:
             return False, f"grid count {occ} != blocks {nl.num_blocks}"
@@ -451,15 +530,24 @@ def _cross_count(n):
     return q3 + (q50 - q3) * (n - 3) / 47.0
 
 
+def _cross_count_vec(counts):
+    """_cross_count over an integer array (same float64 operations)."""
+    n = np.asarray(counts, dtype=np.int64)
+    q3, q50 = 1.0, 2.79
+    return np.where(n <= 3, q3,
+                    np.where(n >= 50, q50 + 0.02616 * (n - 50),
+                             q3 + (q50 - q3) * (n - 3) / 47.0))
+
+
 def anneal_place_gpu(netlist, arch, seed=7, timing_tradeoff=0.5, inner_num=1.0,
                      sta=None, crit_exp=1.0, verbose=False, device="cuda:0",
                      n_moves=None, fixed=None, delay_matrix="analytic",
-                     macros=None):
+                     macros=None, legacy_batches=False):
     """GPU anneal with the same adaptive schedule as the CPU oracle."""
     timing = sta is not None and timing_tradeoff > 0
     placer = GpuPlacer(netlist, arch, seed=seed, timing=timing, device=device,
                        n_moves=n_moves, fixed=fixed, delay_matrix=delay_matrix,
-                       macros=macros)
+                       macros=macros, legacy_batches=legacy_batches)
     nb = netlist.num_blocks
     move_lim = max(256, int(inner_num * (nb ** 1.3333)))
     rlim = float(max(arch.nx, arch.ny))
