@@ -26,6 +26,11 @@ def build_parser():
     p.add_argument("--seed", type=int, default=1)
     # engine selection (reference: --router_algorithm, OptionTokens.c:76-84)
     p.add_argument("--engine", choices=["cpu", "gpu"], default="cpu")
+    p.add_argument("--sta_engine", choices=["cpu", "gpu"], default="cpu",
+                   help="timing engine of the place and route loops: gpu = "
+                        "GpuSTA with delays and criticalities kept on the "
+                        "device (needs --engine gpu); reports use the CPU "
+                        "engine either way")
     p.add_argument("--router_algorithm",
                    choices=["timing_driven", "breadth_first"],
                    default="timing_driven")
@@ -127,6 +132,8 @@ def main(argv=None):
     args = parser.parse_args(argv)
     if args.settings:
         args = apply_settings(parser, args, argv)
+    if args.sta_engine == "gpu" and args.engine != "gpu":
+        parser.error("--sta_engine gpu requires --engine gpu")
     from .arch.archdef import get_arch
     from .arch.xml_parser import parse_arch_xml, size_grid_for_netlist
     from .io.synth import synth_netlist, spec_for_arch
@@ -139,7 +146,7 @@ def main(argv=None):
     from .timing.sta import STA
     from .utils.stats import StatsWriter, routing_stats
     from . import rrgraph
-    from .flow import min_channel_width
+    from .flow import min_channel_width, loop_sta
 
     t_start = time.perf_counter()
     if args.synth:
@@ -175,7 +182,12 @@ def main(argv=None):
         arch.W = args.route_chan_width + (args.route_chan_width % 2)
 
     timing = args.router_algorithm == "timing_driven"
+    # sta: CPU engine for the reports (critical paths, SDC domains);
+    # sta_loop: what the placer and the router refresh timing with
     sta = STA(netlist, arch) if timing else None
+    sta_loop = sta
+    if timing and args.sta_engine == "gpu":
+        sta_loop = loop_sta(netlist, arch, args.engine, args.sta_engine)
     sdc_clocks = {}
     sdc_all = None
     if args.sdc:
@@ -212,7 +224,7 @@ def main(argv=None):
         placement = anneal_place(
             netlist, arch, seed=args.seed,
             timing_tradeoff=args.timing_tradeoff if timing else 0.0,
-            inner_num=args.inner_num, sta=sta, verbose=args.verbose,
+            inner_num=args.inner_num, sta=sta_loop, verbose=args.verbose,
             engine=args.engine, delay_matrix=args.delay_matrix, fixed=fixed,
             crit_exp=args.criticality_exp, macros=macros)
         print(f"placement: bb_cost={placement.bb_cost:.1f} "
@@ -294,7 +306,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         sw = StatsWriter(args.stats_dir) if args.stats_dir else None
         res = pathfinder_route(
-            netlist, placement, g, arch, sta=sta,
+            netlist, placement, g, arch, sta=sta_loop,
             max_iters=args.max_router_iterations,
             pres_fac_init=args.initial_pres_fac,
             pres_fac_mult=args.pres_fac_mult, acc_fac=args.acc_fac,

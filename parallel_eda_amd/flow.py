@@ -24,13 +24,32 @@ class FlowResult:
     times: dict = field(default_factory=dict)
 
 
+def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu"):
+    """The STA engine the place and route loops refresh timing with.
+    "gpu" is GpuSTA(max_crit=1.0): unclamped, so the placer sees what the
+    CPU engine gives it, and the router clamps through max_criticality."""
+    if sta_engine == "cpu":
+        return STA(netlist, arch)
+    if sta_engine != "gpu":
+        raise ValueError(f"sta_engine must be 'cpu' or 'gpu', "
+                         f"got {sta_engine!r}")
+    if engine != "gpu":
+        raise ValueError("sta_engine='gpu' needs engine='gpu'")
+    from .timing.gpu_sta import GpuSTA
+    return GpuSTA(netlist, arch, max_crit=1.0)
+
+
 def run_flow(arch_name: str = "tseng", seed: int = 1, timing_driven: bool = True,
              fill: float = 0.75, max_route_iters: int = 60, verbose: bool = False,
-             engine: str = "cpu", netlist=None, arch: ArchDef = None):
+             engine: str = "cpu", netlist=None, arch: ArchDef = None,
+             sta_engine: str = "cpu"):
+    """sta_engine: "cpu" (timing.sta.STA) or "gpu" (GpuSTA and the
+    device-resident timing loop; needs engine="gpu")."""
     arch = arch or get_arch(arch_name)
     if netlist is None:
         netlist = synth_netlist(spec_for_arch(arch, fill=fill, seed=seed))
-    sta = STA(netlist, arch) if timing_driven else None
+    sta = loop_sta(netlist, arch, engine, sta_engine) if timing_driven \
+        else None
     times = {}
     t0 = time.perf_counter()
     placement = anneal_place(netlist, arch, seed=seed,

@@ -118,7 +118,10 @@ class CpuEngine:
         self.num_nodes = num_nodes
 
     def route_subset(self, crit, pres_fac, net_ids, partial=False,
-                     force_waves=False):
+                     force_waves=False, device_timing=False):
+        if device_timing:
+            raise ValueError("device_timing needs the GPU engine: CpuEngine "
+                             "routes on the host (use timing.sta.STA)")
         import numpy as _np
         self.r.set_pres_fac(pres_fac)
         # refresh pres array from occ under the new pres_fac
@@ -143,7 +146,9 @@ class CpuEngine:
     def set_occ(self, t):
         self.r.set_occ(t.cpu().numpy())
 
-    def sink_delays_local(self, net_ids):
+    def sink_delays_local(self, net_ids, device_timing=False):
+        if device_timing:
+            raise ValueError("device_timing needs the GPU engine")
         return np.asarray(self.r.sink_delays())
 
     def update_acc(self, acc_fac):
@@ -169,11 +174,15 @@ class GpuEngine:
         self._last_sd = np.zeros(router.n_sinks, dtype=np.float32)
 
     def route_subset(self, crit, pres_fac, net_ids, partial=False,
-                     force_waves=False):
+                     force_waves=False, device_timing=False):
+        """device_timing: crit may be a device tensor, and the sink delays
+        stay on the device (sink_delays_local(device_timing=True))."""
         _, sd = self.g.route_iteration(crit, pres_fac, net_subset=net_ids,
                                        fail_ok=True, partial=partial,
-                                       force_waves=force_waves)
-        self._last_sd = sd
+                                       force_waves=force_waves,
+                                       device_delays=device_timing)
+        if not device_timing:
+            self._last_sd = sd
 
     def occ_tensor(self):
         return self.g.t_occ
@@ -181,7 +190,11 @@ class GpuEngine:
     def set_occ(self, t):
         self.g.t_occ.copy_(t)
 
-    def sink_delays_local(self, net_ids):
+    def sink_delays_local(self, net_ids, device_timing=False):
+        if device_timing:
+            # the router's live buffer: current whether or not this rank
+            # routed anything this iteration
+            return self.g.t_sink_delay
         return self._last_sd
 
     def rip_up_nets(self, net_ids):
@@ -352,12 +365,16 @@ class DistRouteLoop:
         return self.set_partition(new_rank)
 
     def iteration(self, crit, pres_fac, acc_fac, active_mask=None,
-                  partial=False, force_waves=False):
+                  partial=False, force_waves=False, device_timing=False):
         """One distributed PathFinder iteration. active_mask: optional
         bool mask over nets (selective reroute); only owned ACTIVE nets
         are routed, but every rank joins the collectives. partial:
         partial rip-up on the engine (keep clean subtrees). Returns
-        (overused_global, sink_delays_global)."""
+        (overused_global, sink_delays_global).
+        device_timing (GPU engine): crit may be a device tensor, and with
+        one rank the returned delays are the router's device buffer; with
+        more ranks they go through the same host-staged all-reduce as
+        ever and come back as numpy."""
         import torch
         dist = _dist() if self.ws > 1 else None
         eng = self.engine
@@ -366,10 +383,18 @@ class DistRouteLoop:
             nets = nets[np.asarray(active_mask)[nets]]
         if self.ws > 1:
             occ_before = eng.occ_tensor().clone()
-        if len(nets):
+        if len(nets) and device_timing:
+            eng.route_subset(crit, pres_fac, nets, partial=partial,
+                             force_waves=force_waves, device_timing=True)
+        elif len(nets):
             eng.route_subset(crit, pres_fac, nets, partial=partial,
                              force_waves=force_waves)
-        sd = eng.sink_delays_local(self.my_nets)
+        if device_timing:
+            sd = eng.sink_delays_local(self.my_nets, device_timing=True)
+            if self.ws > 1:
+                sd = sd.cpu().numpy()
+        else:
+            sd = eng.sink_delays_local(self.my_nets)
         if self.ws > 1:
             occ = eng.occ_tensor()
             delta = occ - occ_before
@@ -391,7 +416,8 @@ class DistRouteLoop:
 def pathfinder_route_dist(loop, cmap, sta, max_iters=60, pres_fac_init=0.5,
                           pres_fac_mult=1.3, acc_fac=1.0,
                           shrink_threshold=128, verbose=False,
-                          incremental=False, intra_delay=0.0):
+                          incremental=False, intra_delay=0.0,
+                          device_timing=None):
     """Distributed PathFinder outer loop (flow-level driver).
 
     Mirrors route.gpu_router.pathfinder_route_gpu's schedule — iteration 1
@@ -407,8 +433,28 @@ def pathfinder_route_dist(loop, cmap, sta, max_iters=60, pres_fac_init=0.5,
     loop: DistRouteLoop; cmap: route.router.ConnMap; sta: timing.sta.STA
     (or None for congestion-only). Returns a dict with success/overused/
     cpd/iters/history.
+
+    device_timing: refresh timing on the device (timing.device_loop.
+    RouteTiming) — None = on exactly when sta is a GpuSTA, False = the
+    host chain below even with one. Needs the GPU engine.
     """
     import time as _time
+    from ..timing.device_loop import (has_device_timing,
+                                      resolve_device_timing, RouteTiming)
+    if sta is not None and has_device_timing(sta) and \
+            isinstance(loop.engine, CpuEngine):
+        raise ValueError(
+            "GpuSTA needs the GPU routing engine (GpuEngine); with "
+            "CpuEngine use the CPU engine timing.sta.STA")
+    device_timing = resolve_device_timing(sta, device_timing)
+    rtiming = None
+    if device_timing:
+        if not isinstance(loop.engine, GpuEngine):
+            raise ValueError(
+                "device timing needs the GPU routing engine (GpuEngine); "
+                f"got {type(loop.engine).__name__}")
+        rtiming = RouteTiming(sta, cmap, intra_delay,
+                              device=loop.engine.g.device)
     n_rsinks = len(loop.my_sink_mask)
     crit = np.zeros(n_rsinks, dtype=np.float32)
     prof = dict(route=0.0, sta=0.0, mask=0.0)
@@ -444,13 +490,23 @@ def pathfinder_route_dist(loop, cmap, sta, max_iters=60, pres_fac_init=0.5,
                        0 < n_act <= 2048)
         prev_overused = overused if overused > 0 else prev_overused
         _t0 = _time.perf_counter()
-        overused, sd = loop.iteration(crit, pres, acc_fac,
-                                      active_mask=active,
-                                      partial=incremental and
-                                      active is not None and not resync,
-                                      force_waves=force_waves)
+        if rtiming is not None:
+            overused, sd = loop.iteration(crit, pres, acc_fac,
+                                          active_mask=active,
+                                          partial=incremental and
+                                          active is not None and not resync,
+                                          force_waves=force_waves,
+                                          device_timing=True)
+        else:
+            overused, sd = loop.iteration(crit, pres, acc_fac,
+                                          active_mask=active,
+                                          partial=incremental and
+                                          active is not None and not resync,
+                                          force_waves=force_waves)
         _t1 = _time.perf_counter()
-        if sta is not None:
+        if rtiming is not None:
+            cpd, crit = rtiming.update(sd)
+        elif sta is not None:
             cmap.conn_delays(sd, out=conn_delay, fill=intra_delay)
             cpd, _slack, c = sta.analyze(conn_delay)
             crit = cmap.sink_crit(c)

@@ -19,12 +19,16 @@ import numpy as np
 def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
                  device="cuda:0", seed=7, timing_driven=True,
                  max_route_iters=80, incremental=True, verbose=False,
-                 inner_num=1.0, check=False):
+                 inner_num=1.0, check=False, sta_engine="cpu"):
     """One complete GPU place+route flow to feasibility (the headline
     benchmark step). The rr graph g (and optionally its device-resident
     upload dev_graph) is the fixed device model — passed in, like the
     FPGA itself. Everything netlist-dependent (placement anneal, net
     terminals, route trees, routing to 0 overused, STA) happens here.
+
+    sta_engine: "cpu" (timing.sta.STA, host refresh) or "gpu" (GpuSTA
+    with the device-resident timing loop in the single-GPU anneal and the
+    route loop; the strip-sharded multi-GPU anneal keeps the CPU engine).
 
     Returns dict(place, route, wirelength, cpd, success, phase_s) —
     rank-identical."""
@@ -35,7 +39,16 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
     from .dist import GpuEngine, DistRouteLoop, pathfinder_route_dist
     from .dist_place import anneal_place_dist
 
+    if sta_engine not in ("cpu", "gpu"):
+        raise ValueError(f"sta_engine must be 'cpu' or 'gpu', "
+                         f"got {sta_engine!r}")
     sta = STA(netlist, arch) if timing_driven else None
+    loop_sta = sta
+    if timing_driven and sta_engine == "gpu":
+        from ..timing.gpu_sta import GpuSTA
+        # unclamped, like the CPU engine: the route loop clamps through
+        # its own max criticality
+        loop_sta = GpuSTA(netlist, arch, device=device, max_crit=1.0)
     tt = 0.5 if timing_driven else 0.0
 
     t0 = time.perf_counter()
@@ -47,7 +60,7 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
                                inner_num=inner_num)
     else:
         pl = anneal_place_gpu(netlist, arch, seed=seed, timing_tradeoff=tt,
-                              sta=sta, device=device, verbose=verbose,
+                              sta=loop_sta, device=device, verbose=verbose,
                               inner_num=inner_num)
     t_place = time.perf_counter() - t0
 
@@ -66,7 +79,8 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
 
     t0 = time.perf_counter()
     res = pathfinder_route_dist(
-        loop, cmap, sta, max_iters=max_route_iters, incremental=incremental,
+        loop, cmap, loop_sta, max_iters=max_route_iters,
+        incremental=incremental,
         verbose=verbose, intra_delay=float(arch.T_opin + arch.T_ipin))
     t_route = time.perf_counter() - t0
     if check and res["success"]:

@@ -542,9 +542,18 @@ def _cross_count_vec(counts):
 def anneal_place_gpu(netlist, arch, seed=7, timing_tradeoff=0.5, inner_num=1.0,
                      sta=None, crit_exp=1.0, verbose=False, device="cuda:0",
                      n_moves=None, fixed=None, delay_matrix="analytic",
-                     macros=None, legacy_batches=False):
-    """GPU anneal with the same adaptive schedule as the CPU oracle."""
+                     macros=None, legacy_batches=False, device_timing=None):
+    """GPU anneal with the same adaptive schedule as the CPU oracle.
+
+    device_timing: refresh criticalities on the device each temperature
+    (timing.device_loop.PlaceTiming: placement -> conn delays -> GpuSTA ->
+    t_conn_crit, nothing copied to the host). None = on exactly when sta
+    is a GpuSTA; False forces the host chain below, which a GpuSTA serves
+    through its numpy analyze()."""
+    import time as _time
+    from ..timing.device_loop import resolve_device_timing, PlaceTiming
     timing = sta is not None and timing_tradeoff > 0
+    device_timing = resolve_device_timing(sta, device_timing) and timing
     placer = GpuPlacer(netlist, arch, seed=seed, timing=timing, device=device,
                        n_moves=n_moves, fixed=fixed, delay_matrix=delay_matrix,
                        macros=macros, legacy_batches=legacy_batches)
@@ -552,9 +561,24 @@ def anneal_place_gpu(netlist, arch, seed=7, timing_tradeoff=0.5, inner_num=1.0,
     move_lim = max(256, int(inner_num * (nb ** 1.3333)))
     rlim = float(max(arch.nx, arch.ny))
     tt = timing_tradeoff if timing else 0.0
+    ptiming = PlaceTiming(placer, sta, crit_exp=crit_exp) \
+        if device_timing else None
+    # time in refresh_crit: every call starts after a host read of device
+    # state and ends in refresh_costs' synchronise
+    prof = {"refresh_s": 0.0, "refreshes": 0}
 
     def refresh_crit():
         if not timing:
+            return
+        _t0 = _time.perf_counter()
+        _refresh_crit()
+        prof["refresh_s"] += _time.perf_counter() - _t0
+        prof["refreshes"] += 1
+
+    def _refresh_crit():
+        if ptiming is not None:
+            ptiming.refresh()
+            placer.refresh_costs()
             return
         # conn delays from current placement via the delay matrix
         bx = placer.t_bx.cpu().numpy(); by = placer.t_by.cpu().numpy()
@@ -630,5 +654,7 @@ def anneal_place_gpu(netlist, arch, seed=7, timing_tradeoff=0.5, inner_num=1.0,
         raise RuntimeError(f"gpu check_place failed: {err}")
     pl = placer.placement()
     pl.stats = {"temps": itemp, "move_lim": move_lim, "history": history,
-                "engine": "gpu"}
+                "engine": "gpu", "device_timing": ptiming is not None,
+                "refresh_s": prof["refresh_s"],
+                "refreshes": prof["refreshes"]}
     return pl

@@ -174,6 +174,11 @@ class GpuRouter:
         self.n_sinks = len(self.sink_rr)
         self.t_net_src = up(self.src_rr)
         self.t_sink_ptr = up(self.sink_ptr)
+        # device-side criticality ordering (route_iteration with a device
+        # crit tensor): sinks in original order, and the net of each
+        self.t_sink_rr0 = up(self.sink_rr)
+        self.t_net_of_sink = up(np.repeat(
+            np.arange(self.num_nets, dtype=np.int32), np.diff(self.sink_ptr)))
 
         # bounding boxes (terminal bb + margin)
         self.bb_margin_per_net = np.full(self.num_nets, bb_margin, dtype=np.int32)
@@ -390,10 +395,28 @@ class GpuRouter:
                                  self.arch.nx, self.arch.ny)
 
     # ---- one PathFinder iteration ----
+    def sink_order_device(self, t_crit):
+        """Device twin of np.lexsort((-crit, net_of_sink)): sinks by net,
+        within a net by decreasing criticality, ties in original order.
+        Two stable sorts (by descending crit, then by net). Adding +0.0
+        first turns -0.0 into +0.0, so the two zeros tie under any sort
+        implementation, as they do in lexsort. Returns the int64
+        permutation (device)."""
+        torch = self.torch
+        key = t_crit + 0.0
+        i1 = torch.sort(key, descending=True, stable=True).indices
+        i2 = torch.sort(self.t_net_of_sink[i1], stable=True).indices
+        return i1[i2]
+
     def route_iteration(self, crit, pres_fac, net_subset=None, fail_ok=False,
-                        partial=False, force_waves=False):
-        """crit: per-sink criticality aligned with sink_rr (original order).
+                        partial=False, force_waves=False,
+                        device_delays=False):
+        """crit: per-sink criticality aligned with sink_rr (original order);
+        a numpy array, or a float32 device tensor (device-resident timing
+        loop: the ordering then runs on the device, no upload).
         Returns (overused_count, sink_delays aligned with original order).
+        device_delays: return self.t_sink_delay itself (the live device
+        buffer) instead of a host copy.
         net_subset: optional array of net ids to (re)route; others keep
         their route trees (multi-GPU partitioning / selective reroute).
         fail_ok: exhausted retries leave the stragglers partially routed
@@ -413,11 +436,22 @@ class GpuRouter:
                              launches=0)
         _tp = _time.perf_counter()
         # order sinks by decreasing criticality within each net
-        net_of_sink = np.repeat(np.arange(self.num_nets), np.diff(self.sink_ptr))
-        perm = np.lexsort((-crit, net_of_sink))
-        t_sink_rr = torch.from_numpy(self.sink_rr[perm]).to(self.device)
-        t_crit = torch.from_numpy(np.ascontiguousarray(crit[perm], dtype=np.float32)).to(self.device)
-        t_sink_orig = torch.from_numpy(perm.astype(np.int32)).to(self.device)
+        if torch.is_tensor(crit):
+            if (not crit.is_cuda or crit.dtype != torch.float32
+                    or crit.numel() != self.n_sinks):
+                raise ValueError(
+                    f"crit tensor: need {self.n_sinks} float32 on the device, "
+                    f"got {crit.dtype} x {crit.numel()} on {crit.device}")
+            t_perm = self.sink_order_device(crit.reshape(-1))
+            t_sink_rr = self.t_sink_rr0[t_perm]
+            t_crit = crit.reshape(-1)[t_perm]
+            t_sink_orig = t_perm.to(torch.int32)
+        else:
+            net_of_sink = np.repeat(np.arange(self.num_nets), np.diff(self.sink_ptr))
+            perm = np.lexsort((-crit, net_of_sink))
+            t_sink_rr = torch.from_numpy(self.sink_rr[perm]).to(self.device)
+            t_crit = torch.from_numpy(np.ascontiguousarray(crit[perm], dtype=np.float32)).to(self.device)
+            t_sink_orig = torch.from_numpy(perm.astype(np.int32)).to(self.device)
 
         todo = (np.arange(self.num_nets, dtype=np.int64) if net_subset is None
                 else np.asarray(net_subset, dtype=np.int64))
@@ -599,6 +633,8 @@ class GpuRouter:
             todo = failed
 
         overused = int((self.t_occ > self.t_cap.to(torch.int32)).sum().item())
+        if device_delays:
+            return overused, self.t_sink_delay
         sink_delays = self.t_sink_delay.cpu().numpy()
         return overused, sink_delays
 
@@ -683,6 +719,11 @@ class GpuRouter:
                 self.t_tree_sw[o0:o0 + ln].cpu().numpy(),
                 self.t_tree_delay[o0:o0 + ln].cpu().numpy())
 
+    def tree(self, inet):
+        """Route tree of net inet under the CPU router's name for it, which
+        the CLI's statistics and writers call on either engine."""
+        return self.get_tree(inet)
+
     def _make_args(self, t_sink_rr, t_crit, t_sink_orig, q_small, q_large,
                    pres_fac):
         a = hip_api.RouteLaunchArgs()
@@ -749,11 +790,18 @@ def pathfinder_route_gpu(netlist, placement, g, arch, sta=None, max_iters=60,
                          astar_fac=1.2, verbose=False, device="cuda:0",
                          rip_up_always=False, deterministic=False,
                          bb_factor=4, crit_exp=1.0, max_criticality=0.99,
-                         incremental=False):
+                         incremental=False, device_timing=None):
     """GPU PathFinder outer loop — mirrors route.router.pathfinder_route.
 
     bb_factor: initial per-net bounding-box margin in tiles (reference:
-    -bb_factor route option); grown automatically on route failure."""
+    -bb_factor route option); grown automatically on route failure.
+    device_timing: run the per-iteration timing refresh on the device
+    (timing.device_loop.RouteTiming; sink delays and criticalities stay in
+    HBM). None = on exactly when sta is a GpuSTA; False forces the host
+    chain, which a GpuSTA serves through its numpy analyze()."""
+    import time as _time
+    from ..timing.device_loop import resolve_device_timing, RouteTiming
+    device_timing = resolve_device_timing(sta, device_timing)
     net_ids, src_rr, sink_ptr, sink_rr, conn_index = net_rr_terminals(
         netlist, placement, g, arch)
     from .router import ConnMap
@@ -765,6 +813,12 @@ def pathfinder_route_gpu(netlist, placement, g, arch, sta=None, max_iters=60,
     crit = np.zeros(n_rsinks, dtype=np.float32)
     conn_delay = np.zeros(netlist.num_conns, dtype=np.float32)
     intra_delay = float(arch.T_opin + arch.T_ipin)
+    rtiming = None
+    if device_timing:
+        rtiming = RouteTiming(sta, cmap, intra_delay,
+                              max_crit=max_criticality, crit_exp=crit_exp,
+                              device=device)
+    t_sta = 0.0
     pres_fac = 0.0   # first iteration: congestion-blind (VPR style)
     cpd = 0.0
     history = []
@@ -803,7 +857,7 @@ def pathfinder_route_gpu(netlist, placement, g, arch, sta=None, max_iters=60,
         overused, sink_delays = router.route_iteration(
             crit, pres_fac, net_subset=subset,
             partial=incremental and subset is not None and not resync,
-            force_waves=force_waves)
+            force_waves=force_waves, device_delays=rtiming is not None)
         st = router.search_stats()
         history.append(dict(iter=it, overused=int(overused), cpd=cpd,
                             rounds=st["rounds"], scanned=st["scanned"],
@@ -818,11 +872,17 @@ def pathfinder_route_gpu(netlist, placement, g, arch, sta=None, max_iters=60,
             # updates; off by default (costs one kernel + compare)
             if not router.check_occ_recount():
                 raise RuntimeError(f"occ recount mismatch at iteration {it}")
-        if sta is not None:
+        # route_iteration ended on a host read and both refresh chains end
+        # on one, so the host clock brackets finished device work
+        _t0 = _time.perf_counter()
+        if rtiming is not None:
+            cpd, crit = rtiming.update(sink_delays)
+        elif sta is not None:
             cmap.conn_delays(sink_delays, out=conn_delay, fill=intra_delay)
             cpd, slack, c = sta.analyze(conn_delay)
             crit = cmap.sink_crit(c, max_crit=max_criticality,
                                   crit_exp=crit_exp)
+        t_sta += _time.perf_counter() - _t0
         if overused == 0:
             break
         pres_fac = pres_fac_init if pres_fac == 0.0 else pres_fac * pres_fac_mult
@@ -834,5 +894,7 @@ def pathfinder_route_gpu(netlist, placement, g, arch, sta=None, max_iters=60,
     return RouteResult(success=ok, iterations=it, overused=int(overused),
                        wirelength=router.wirelength(), crit_path_delay=cpd,
                        stats={"history": history,
-                              "num_routed_nets": len(net_ids)},
+                              "num_routed_nets": len(net_ids),
+                              "prof": {"sta": t_sta},
+                              "device_timing": rtiming is not None},
                        router=router)

@@ -1,0 +1,485 @@
+"""Device-resident timing loop (csrc/hip/timing_loop.hip,
+timing/device_loop.py): the glue kernels against numpy, PlaceTiming and
+RouteTiming against the host refresh chains they replace, and the loops
+and flows that use them.
+
+The glue is gathers and a max, so it is held to bit equality; only the
+powf branch and the CPU-vs-GPU STA comparison carry a tolerance. The
+cases are the smallest real shapes (tiny 6x6, tiny_het 10x8 — not square,
+which catches a gx/gy stride mix-up — and tseng 14x14); in all three every
+connection has its own routed sink, so the fill and shared-sink branches
+are covered by a synthetic ConnMap instead."""
+import ctypes as ct
+import functools
+import types
+
+import numpy as np
+import pytest
+
+from parallel_eda_amd.arch.archdef import get_arch
+from parallel_eda_amd.io.synth import synth_netlist, spec_for_arch
+from parallel_eda_amd.route.router import ConnMap, net_rr_terminals
+from parallel_eda_amd.timing.sta import STA
+from parallel_eda_amd.timing import device_loop
+
+gpu = pytest.mark.gpu
+
+CASES = {"tiny": (0.6, 2), "tiny_het": (0.6, 1), "tseng": (0.5, 4)}
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    fill, seed = CASES[name]
+    arch = get_arch(name)
+    return arch, synth_netlist(spec_for_arch(arch, fill=fill, seed=seed)), seed
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same_bits(got, want, what):
+    got, want = _bits(got), _bits(want)
+    assert got.shape == want.shape, what
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, f"{what}: {len(bad)} differ, first at {bad[:5]}"
+
+
+def _host_place_delays(nl, dm, bx, by):
+    net_of_conn = np.repeat(np.arange(nl.num_nets), np.diff(nl.net_sink_ptr))
+    drv = nl.net_driver[net_of_conn]
+    return dm[np.abs(bx[nl.net_sinks] - bx[drv]),
+              np.abs(by[nl.net_sinks] - by[drv])]
+
+
+def _dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
+
+
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _p(t):
+    return ct.c_void_p(t.data_ptr())
+
+
+# ---- synthetic ConnMap: unmapped connections, empty and shared sinks ----
+
+N_CONNS, N_RSINKS = 1000, 700
+
+
+@functools.lru_cache(maxsize=None)
+def _synthetic_map():
+    """1,000 connections on 700 routed sinks: 100 connections unmapped,
+    50 sinks without a connection, the rest with 1 to 5, in shuffled
+    order. Returns (cmap, per-sink connection counts)."""
+    rng = np.random.default_rng(11)
+    mapped = rng.permutation(N_CONNS)[:900]
+    counts = np.zeros(N_RSINKS, dtype=np.int64)
+    used = rng.permutation(N_RSINKS)[:650]
+    counts[used] = 1
+    counts[used[0]] = 5
+    left = 900 - int(counts.sum())
+    while left:
+        s = used[rng.integers(len(used))]
+        if counts[s] < 5:
+            counts[s] += 1
+            left -= 1
+    rsink = rng.permutation(np.repeat(np.arange(N_RSINKS), counts))
+    cmap = ConnMap([(mapped, rsink)], np.asarray([0, N_RSINKS]),
+                   N_CONNS, N_RSINKS)
+    return cmap, counts
+
+
+def _synthetic_crit(cmap, counts):
+    """Connection criticalities with exact ties at a sink's maximum,
+    all-zero sinks, and values above the 0.99 clamp."""
+    rng = np.random.default_rng(12)
+    cc = rng.random(N_CONNS).astype(np.float32)
+    by_sink = [cmap.conn[cmap.rsink == s] for s in range(N_RSINKS)]
+    multi = [s for s in range(N_RSINKS) if counts[s] >= 2]
+    for s in multi[:40]:            # the maximum is held by two connections
+        cc[by_sink[s][:2]] = cc[by_sink[s]].max()
+    for s in multi[40:70]:          # every connection of the sink at zero
+        cc[by_sink[s]] = 0.0
+    for s in multi[70:90]:          # above the clamp, 1.0 included
+        cc[by_sink[s][0]] = 0.995
+        cc[by_sink[s][1]] = 1.0
+    return cc
+
+
+def test_synthetic_map_shape():
+    cmap, counts = _synthetic_map()
+    assert counts.min() == 0 and counts.max() == 5
+    assert (counts == 0).sum() == 50 and counts.sum() == 900
+    assert len(np.unique(cmap.conn)) == 900
+    assert not np.all(np.diff(cmap.rsink) >= 0)      # shuffled
+
+
+def test_host_tables_reproduce_connmap():
+    """The two tables the kernels read, replayed in numpy, give
+    ConnMap.conn_delays and ConnMap.sink_crit exactly."""
+    cmap, counts = _synthetic_map()
+    cc = _synthetic_crit(cmap, counts)
+    rng = np.random.default_rng(13)
+    sd = (rng.random(N_RSINKS) * 2e-9).astype(np.float32)
+    cr = device_loop.conn_rsink_map(cmap)
+    assert cr.dtype == np.int32 and (cr < 0).sum() == 100
+    got = np.where(cr < 0, np.float32(1.5e-10), sd[np.maximum(cr, 0)])
+    _same_bits(got, cmap.conn_delays(sd, fill=1.5e-10), "conn delays")
+    rs_ptr, rs_conn = device_loop.rsink_conn_csr(cmap)
+    assert rs_ptr.dtype == np.int64 and rs_conn.dtype == np.int32
+    assert np.array_equal(np.diff(rs_ptr), counts)
+    got = np.asarray([min(max([0.0] + cc[rs_conn[a:b]].tolist()), 0.99)
+                      for a, b in zip(rs_ptr[:-1], rs_ptr[1:])],
+                     dtype=np.float64).astype(np.float32)
+    want = cmap.sink_crit(cc, max_crit=0.99)
+    assert np.array_equal(got, np.minimum(want, np.float32(0.99)))
+    bad = ConnMap([(np.asarray([N_CONNS]), np.asarray([0]))],
+                  np.asarray([0, N_RSINKS]), N_CONNS, N_RSINKS)
+    with pytest.raises(ValueError):
+        device_loop.conn_rsink_map(bad)
+
+
+# ---- public interface, CPU side ----
+
+def test_cli_accepts_sta_engine():
+    from parallel_eda_amd.__main__ import build_parser, main
+    p = build_parser()
+    assert p.parse_args(["--synth", "tiny"]).sta_engine == "cpu"
+    a = p.parse_args(["--synth", "tiny", "--engine", "gpu",
+                      "--sta_engine", "gpu"])
+    assert a.sta_engine == "gpu" and a.engine == "gpu"
+    with pytest.raises(SystemExit):
+        p.parse_args(["--synth", "tiny", "--sta_engine", "hip"])
+    # gpu timing without the gpu engine is refused before any work
+    with pytest.raises(SystemExit) as e:
+        main(["--synth", "tiny", "--sta_engine", "gpu"])
+    assert e.value.code == 2
+
+
+def test_sta_engine_selection_rules():
+    from parallel_eda_amd.flow import loop_sta
+    arch, nl, _ = _case("tiny")
+    assert isinstance(loop_sta(nl, arch), STA)
+    with pytest.raises(ValueError):
+        loop_sta(nl, arch, engine="cpu", sta_engine="gpu")
+    with pytest.raises(ValueError):
+        loop_sta(nl, arch, engine="gpu", sta_engine="hip")
+    cpu_sta = STA(nl, arch)
+    assert device_loop.resolve_device_timing(None, None) is False
+    assert device_loop.resolve_device_timing(cpu_sta, None) is False
+    assert device_loop.resolve_device_timing(cpu_sta, False) is False
+    with pytest.raises(ValueError):
+        device_loop.resolve_device_timing(cpu_sta, True)
+    fake = types.SimpleNamespace(analyze_device=None)
+    assert device_loop.resolve_device_timing(fake, None) is True
+    assert device_loop.resolve_device_timing(fake, False) is False
+
+
+@gpu
+def test_cli_flow_with_gpu_sta(capsys):
+    """The whole CLI flow on the GPU engines with device timing, through
+    the post-route statistics (which read the router's trees)."""
+    from parallel_eda_amd.__main__ import main
+    assert main(["--synth", "tiny", "--fill", "0.6", "--seed", "2",
+                 "--engine", "gpu", "--sta_engine", "gpu"]) == 0
+    out = capsys.readouterr().out
+    assert "routed in" in out and "segments=" in out
+
+
+# ---- 1. place conn-delay kernel, exact ----
+
+@gpu
+@pytest.mark.parametrize("name", ["tiny_het", "tseng"])
+def test_place_conn_delay_exact(name):
+    import torch
+    from parallel_eda_amd.place.gpu_placer import GpuPlacer
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, seed = _case(name)
+    p = GpuPlacer(nl, arch, seed=seed, timing=True)
+    gsta = GpuSTA(nl, arch, max_crit=1.0)
+    net_of_conn = np.repeat(np.arange(nl.num_nets), np.diff(nl.net_sink_ptr))
+    assert np.array_equal(gsta.t_conn_driver.cpu().numpy(),
+                          nl.net_driver[net_of_conn])
+    assert p._dm.shape == (p.gx, p.gy)
+    out = torch.full((nl.num_conns,), -1.0, dtype=torch.float32,
+                     device="cuda:0")
+    rc = device_loop._lib().pnr_tl_place_conn_delay(
+        _p(p.t_bx), _p(p.t_by), _p(gsta.t_conn_driver), _p(gsta.t_conn_sink),
+        _p(p.t_delay_mat), p.gy, nl.num_conns, _p(out), _stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    want = _host_place_delays(nl, p._dm, p.t_bx.cpu().numpy(),
+                              p.t_by.cpu().numpy())
+    _same_bits(out.cpu().numpy(), want, f"{name} conn delays")
+
+
+@gpu
+def test_place_conn_delay_synthetic_grid_stride():
+    """40x30 grid, 600,001 connections: more than the 2048 x 256 threads
+    of one pass and odd, so the stride loop and the tail both run."""
+    import torch
+    gx, gy, nb, nc = 40, 30, 5000, 600_001
+    assert nc > 2048 * 256 and nc % 2 == 1
+    rng = np.random.default_rng(5)
+    bx = rng.integers(0, gx, nb).astype(np.int32)
+    by = rng.integers(0, gy, nb).astype(np.int32)
+    bx[:6] = [7, 7, 0, gx - 1, 0, gx - 1]       # 0,1 share a tile;
+    by[:6] = [9, 9, 0, gy - 1, gy - 1, 0]       # 2..5 are the corners
+    drv = rng.integers(0, nb, nc).astype(np.int32)
+    snk = rng.integers(0, nb, nc).astype(np.int32)
+    drv[:5] = [0, 2, 3, 4, 1]
+    snk[:5] = [1, 3, 2, 5, 1]
+    drv[-1], snk[-1] = 5, 4                     # the tail element
+    dm = rng.random((gx, gy)).astype(np.float32)
+    dx = np.abs(bx[snk] - bx[drv]); dy = np.abs(by[snk] - by[drv])
+    assert dx[0] == 0 and dy[0] == 0
+    assert dx[1] == gx - 1 and dy[1] == gy - 1
+    want = dm[dx, dy]
+    t = [_dev(a) for a in (bx, by, drv, snk, dm.ravel())]
+    out = torch.full((nc,), -1.0, dtype=torch.float32, device="cuda:0")
+    rc = device_loop._lib().pnr_tl_place_conn_delay(
+        _p(t[0]), _p(t[1]), _p(t[2]), _p(t[3]), _p(t[4]), gy, nc, _p(out),
+        _stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    _same_bits(out.cpu().numpy(), want, "synthetic conn delays")
+
+
+# ---- 2. router glue on the synthetic ConnMap ----
+
+def _ulp_diff(a, b):
+    """Distance in float32 steps (both arrays non-negative)."""
+    return np.abs(_bits(a).astype(np.int64) - _bits(b).astype(np.int64))
+
+
+@gpu
+def test_router_glue_synthetic_map():
+    import torch
+    cmap, counts = _synthetic_map()
+    cc = _synthetic_crit(cmap, counts)
+    lib = device_loop._lib()
+    rng = np.random.default_rng(13)
+    sd = (rng.random(N_RSINKS) * 2e-9).astype(np.float32)
+    fill = 1.5e-10
+    t_cr = _dev(device_loop.conn_rsink_map(cmap))
+    rs_ptr, rs_conn = device_loop.rsink_conn_csr(cmap)
+    t_ptr, t_conn = _dev(rs_ptr), _dev(rs_conn)
+    t_sd, t_cc = _dev(sd), _dev(cc)
+
+    out = torch.full((N_CONNS,), -1.0, dtype=torch.float32, device="cuda:0")
+    rc = lib.pnr_tl_conn_delay_from_sinks(_p(t_sd), _p(t_cr), fill, N_CONNS,
+                                          _p(out), _stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    _same_bits(out.cpu().numpy(), cmap.conn_delays(sd, fill=fill),
+               "conn delays from sinks")
+
+    def sink_crit(crit_exp):
+        o = torch.full((N_RSINKS,), -1.0, dtype=torch.float32,
+                       device="cuda:0")
+        rc = lib.pnr_tl_sink_crit(_p(t_cc), _p(t_ptr), _p(t_conn), N_RSINKS,
+                                  crit_exp, 0.99, _p(o), _stream())
+        assert rc == 0
+        torch.cuda.synchronize()
+        return o.cpu().numpy()
+
+    want = cmap.sink_crit(cc, max_crit=0.99)
+    assert (want == 0).sum() >= 50 + 30 and (want == np.float32(0.99)).any()
+    _same_bits(sink_crit(1.0), want, "sink crit")
+
+    # the exponent: numpy's float32 power is the reference. 16 ulp is
+    # pow's bound in the OpenCL accuracy table the device math library is
+    # built to, plus 1 for numpy's own rounding.
+    got = sink_crit(2.5)
+    want = cmap.sink_crit(cc, max_crit=0.99, crit_exp=2.5)
+    ulp = _ulp_diff(got, want)
+    print(f"sink_crit crit_exp=2.5: max ulp difference {int(ulp.max())}")
+    assert ulp.max() <= 17
+
+    # crit_pow: a copy at 1.0, powf otherwise
+    o = torch.full((N_CONNS,), -1.0, dtype=torch.float32, device="cuda:0")
+    assert lib.pnr_tl_crit_pow(_p(t_cc), 1.0, N_CONNS, _p(o), _stream()) == 0
+    torch.cuda.synchronize()
+    _same_bits(o.cpu().numpy(), cc, "crit_pow copy")
+    assert lib.pnr_tl_crit_pow(_p(t_cc), 2.5, N_CONNS, _p(o), _stream()) == 0
+    torch.cuda.synchronize()
+    ulp = _ulp_diff(o.cpu().numpy(), np.power(cc, np.float32(2.5)))
+    print(f"crit_pow crit_exp=2.5: max ulp difference {int(ulp.max())}")
+    assert ulp.max() <= 17
+
+
+# ---- 3. PlaceTiming.refresh against the CPU oracle ----
+
+@gpu
+@pytest.mark.parametrize("name", ["tseng", "tiny_het"])
+def test_place_timing_refresh_matches_cpu_sta(name):
+    import torch
+    from parallel_eda_amd.place.gpu_placer import GpuPlacer
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, seed = _case(name)
+    p = GpuPlacer(nl, arch, seed=seed, timing=True)
+    pt = device_loop.PlaceTiming(p, GpuSTA(nl, arch, max_crit=1.0))
+    t_cpd = pt.refresh()
+    torch.cuda.synchronize()
+    # the host refresh_crit chain of anneal_place_gpu with the CPU engine
+    d = _host_place_delays(nl, p._dm, p.t_bx.cpu().numpy(),
+                           p.t_by.cpu().numpy())
+    cpd, _slack, c = STA(nl, arch).analyze(d)
+    want = np.asarray(c) ** 1.0
+    got = p.t_conn_crit.cpu().numpy()
+    assert want.max() > 0.99            # unclamped, like the CPU engine
+    assert np.allclose(got, want, rtol=1e-4, atol=1e-5)
+    assert float(t_cpd.item()) == pytest.approx(cpd, rel=1e-5)
+
+
+# ---- 4. whole anneal: device path equals host path, same engine ----
+
+@gpu
+@pytest.mark.parametrize("name", ["tseng", "tiny_het"])
+def test_anneal_device_timing_matches_host(name):
+    from parallel_eda_amd.place.gpu_placer import anneal_place_gpu
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, _ = _case(name)
+    res = []
+    for dev in (False, True):
+        res.append(anneal_place_gpu(
+            nl, arch, seed=7, timing_tradeoff=0.5,
+            sta=GpuSTA(nl, arch, max_crit=1.0), device_timing=dev))
+    host, devp = res
+    assert devp.stats["device_timing"] and not host.stats["device_timing"]
+    for k in ("x", "y", "slot"):
+        assert np.array_equal(np.asarray(getattr(devp, k)),
+                              np.asarray(getattr(host, k))), k
+    assert devp.bb_cost == host.bb_cost
+    assert devp.td_cost == host.td_cost and devp.td_cost > 0
+    assert devp.stats["temps"] == host.stats["temps"]
+    assert devp.stats["history"] == host.stats["history"]
+
+
+# ---- 5. router lockstep ----
+
+@functools.lru_cache(maxsize=None)
+def _placed(name):
+    from parallel_eda_amd.place.placer import anneal_place
+    from parallel_eda_amd import rrgraph
+    arch, nl, seed = _case(name)
+    pl = anneal_place(nl, arch, seed=seed, timing_tradeoff=0.0)
+    g = rrgraph.build_rr_graph(arch)
+    return arch, nl, pl, g
+
+
+@gpu
+@pytest.mark.parametrize("name", ["tiny", "tseng"])
+def test_router_lockstep(name):
+    """Each iteration the device refresh and the device sink order equal
+    the host chain run on the same engine and the same delays; the device
+    tensor then drives the next iteration."""
+    import torch
+    from parallel_eda_amd.route.gpu_router import GpuRouter
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, pl, g = _placed(name)
+    net_ids, src_rr, sink_ptr, sink_rr, conn_index = net_rr_terminals(
+        nl, pl, g, arch)
+    r = GpuRouter(g, arch, src_rr, sink_ptr.astype(np.int32), sink_rr)
+    cmap = ConnMap(conn_index, sink_ptr, nl.num_conns, len(sink_rr))
+    gsta = GpuSTA(nl, arch, max_crit=1.0)
+    intra = float(arch.T_opin + arch.T_ipin)
+    rt = device_loop.RouteTiming(gsta, cmap, intra, max_crit=0.99)
+    net_of_sink = np.repeat(np.arange(r.num_nets), np.diff(r.sink_ptr))
+    crit = np.zeros(len(sink_rr), dtype=np.float32)
+    pres = 0.0
+    for it in range(4):
+        _over, sd = r.route_iteration(crit, pres, device_delays=True)
+        assert sd is r.t_sink_delay
+        cd = cmap.conn_delays(r.t_sink_delay.cpu().numpy(), fill=intra)
+        cpd_h, _slack, c = gsta.analyze(cd)
+        crit_h = cmap.sink_crit(c, max_crit=0.99)
+        cpd_d, t_crit = rt.update(r.t_sink_delay)
+        assert cpd_d == cpd_h and cpd_d > 0
+        assert np.array_equal(t_crit.cpu().numpy(), crit_h), it
+        assert crit_h.max() > 0
+        perm_d = r.sink_order_device(t_crit).cpu().numpy()
+        assert np.array_equal(perm_d, np.lexsort((-crit_h, net_of_sink))), it
+        # a numpy upload takes the same path as the device tensor
+        cpd_u, t_crit_u = rt.update(r.t_sink_delay.cpu().numpy())
+        assert cpd_u == cpd_h
+        assert np.array_equal(t_crit_u.cpu().numpy(), crit_h)
+        crit = t_crit
+        pres = 0.5 if pres == 0.0 else pres * 1.3
+        r.update_acc(1.0)
+    assert r.check_occ_recount()
+    # ties and both zeros: the order is lexsort's, ties included
+    rng = np.random.default_rng(3)
+    lv = np.asarray([0.0, -0.0, 0.25, 0.5, 0.99], dtype=np.float32)
+    c = lv[rng.integers(0, len(lv), len(sink_rr))]
+    perm_d = r.sink_order_device(_dev(c)).cpu().numpy()
+    assert np.array_equal(perm_d, np.lexsort((-c, net_of_sink)))
+    with pytest.raises(ValueError):
+        r.route_iteration(torch.zeros(len(sink_rr) + 1, device="cuda:0"), pres)
+
+
+# ---- 6. flow level ----
+
+@functools.lru_cache(maxsize=None)
+def _tseng_cpu_sta_route():
+    """The gate's reference: the GPU router with the CPU STA."""
+    from parallel_eda_amd.route.gpu_router import pathfinder_route_gpu
+    arch, nl, pl, g = _placed("tseng")
+    res = pathfinder_route_gpu(nl, pl, g, arch, sta=STA(nl, arch),
+                               max_iters=60)
+    assert res.success and not res.stats["device_timing"]
+    return res.crit_path_delay, res.wirelength
+
+
+@gpu
+def test_pathfinder_route_gpu_with_gpu_sta():
+    from parallel_eda_amd.route.gpu_router import pathfinder_route_gpu
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, pl, g = _placed("tseng")
+    cpd_ref, wl_ref = _tseng_cpu_sta_route()
+    res = pathfinder_route_gpu(nl, pl, g, arch,
+                               sta=GpuSTA(nl, arch, max_crit=1.0),
+                               max_iters=60)
+    assert res.success, f"overused={res.overused}"
+    assert res.stats["device_timing"]
+    assert res.router.check_occ_recount()
+    assert 0 < res.crit_path_delay <= cpd_ref * 1.10, (
+        f"cpd {res.crit_path_delay} vs {cpd_ref}")
+    assert res.wirelength <= wl_ref * 1.10, (
+        f"WL {res.wirelength} vs {wl_ref}")
+
+
+@gpu
+def test_pathfinder_route_dist_with_gpu_sta():
+    """World size 1, built as full_flow.run_flow_gpu builds it."""
+    from parallel_eda_amd.route.gpu_router import GpuRouter, DevGraph
+    from parallel_eda_amd.parallel.dist import (GpuEngine, CpuEngine,
+                                                DistRouteLoop,
+                                                pathfinder_route_dist)
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    arch, nl, pl, g = _placed("tseng")
+    cpd_ref, wl_ref = _tseng_cpu_sta_route()
+    net_ids, src_rr, sink_ptr, sink_rr, conn_index = net_rr_terminals(
+        nl, pl, g, arch)
+    cmap = ConnMap(conn_index, sink_ptr, nl.num_conns, len(sink_rr))
+    router = GpuRouter(g, arch, src_rr, sink_ptr.astype(np.int32), sink_rr,
+                       dev_graph=DevGraph(g, arch, "cuda:0"))
+    loop = DistRouteLoop(GpuEngine(router), len(net_ids), router.bb,
+                         len(sink_rr), sink_ptr, rank=0, world_size=1)
+    gsta = GpuSTA(nl, arch, max_crit=1.0)
+    res = pathfinder_route_dist(
+        loop, cmap, gsta, max_iters=80, incremental=True,
+        intra_delay=float(arch.T_opin + arch.T_ipin))
+    assert res["success"], f"overused={res['overused']}"
+    assert router.check_occ_recount()
+    assert 0 < res["cpd"] <= cpd_ref * 1.10, f"cpd {res['cpd']} vs {cpd_ref}"
+    assert router.wirelength() <= wl_ref * 1.10
+    # the CPU routing engine cannot be paired with the GPU timing engine
+    cpu_loop = types.SimpleNamespace(engine=CpuEngine(None, 0))
+    with pytest.raises(ValueError, match="GpuSTA"):
+        pathfinder_route_dist(cpu_loop, cmap, gsta)

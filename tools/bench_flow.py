@@ -37,6 +37,10 @@ def main():
     ap.add_argument("--max_iters", type=int, default=60)
     ap.add_argument("--incremental", action="store_true",
                     help="partial rip-up on selective iterations")
+    ap.add_argument("--sta_engine", choices=["cpu", "gpu"], default="cpu",
+                    help="timing engine of the place and route loops; gpu "
+                         "needs the gpu router (and the gpu placer unless "
+                         "the placement is synthetic)")
     args = ap.parse_args()
 
     from parallel_eda_amd.arch.archdef import get_arch
@@ -46,6 +50,7 @@ def main():
     from parallel_eda_amd.route.router import pathfinder_route
     from parallel_eda_amd.timing.sta import STA
     from parallel_eda_amd import rrgraph
+    from parallel_eda_amd.flow import loop_sta
 
     try:
         import torch
@@ -68,7 +73,7 @@ def main():
         nl = synth_netlist(spec_for_arch(arch, fill=args.fill,
                                          seed=args.seed))
         t_synth = time.perf_counter() - t0
-        sta_p = STA(nl, arch)
+        sta_p = loop_sta(nl, arch, placer, args.sta_engine)
         t1 = time.perf_counter()
         pl = anneal_place(nl, arch, seed=args.seed, timing_tradeoff=0.5,
                           sta=sta_p, engine=placer)
@@ -77,7 +82,7 @@ def main():
     g = rrgraph.build_rr_graph(arch)
     t_rr = time.perf_counter() - t1
 
-    sta = STA(nl, arch)
+    sta = loop_sta(nl, arch, router, args.sta_engine)
     t1 = time.perf_counter()
     res = pathfinder_route(nl, pl, g, arch, sta=sta,
                            max_iters=args.max_iters, engine=router,
@@ -92,11 +97,16 @@ def main():
         "config": {"model": args.config, "grid": f"{arch.nx}x{arch.ny}",
                    "W": arch.W, "nets": int(nl.num_nets),
                    "sinks": int(nl.num_conns), "placer": placer,
-                   "router": router, "incremental": args.incremental},
+                   "router": router, "incremental": args.incremental,
+                   "sta_engine": args.sta_engine},
         "success": bool(res.success),
         "route_iterations": int(res.iterations),
         "wirelength": int(res.wirelength),
         "crit_path_ns": round(res.crit_path_delay * 1e9, 4),
+        # timing-refresh shares (GPU engines; None where not recorded)
+        "route_sta_s": res.stats.get("prof", {}).get("sta"),
+        "place_refresh_s": getattr(pl, "stats", {}).get("refresh_s"),
+        "place_temps": getattr(pl, "stats", {}).get("temps"),
         "phase_s": {"netlist_synth": round(t_synth, 3),
                     "place": round(t_place, 3),
                     "rr_build": round(t_rr, 3),
