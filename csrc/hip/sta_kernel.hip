@@ -164,7 +164,7 @@ __global__ void sta_slack_domains(StaDev s, const float* __restrict__ delay,
                                   const float* __restrict__ req_all,
                                   const float* __restrict__ periods, int K,
                                   float* slack, float* crit, float max_crit,
-                                  unsigned* worst_bits /*achieved period*/) {
+                                  unsigned long long* worst /*packed, below*/) {
   const float NEG = -3.0e38f, POS = 3.0e38f;
   int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   int64_t total = s.num_conns * (int64_t)K * K;
@@ -196,10 +196,14 @@ __global__ void sta_slack_domains(StaDev s, const float* __restrict__ delay,
     cr = fminf(fmaxf(cr, 0.0f), max_crit);
     atomicMax((unsigned*)&crit[c], __float_as_uint(cr));  // cr >= 0
     float achieved = constraint - sl;
-    // track the worst achieved/constraint ratio's achieved period
-    unsigned ab = __float_as_uint(achieved / constraint);
-    unsigned prev = atomicMax(&worst_bits[0], ab);
-    if (ab > prev) worst_bits[1] = __float_as_uint(achieved);
+    // track the worst achieved/constraint ratio's achieved period: one
+    // 64-bit max on (ratio bits << 32) | achieved bits, so the period
+    // always belongs to the winning ratio. Both are non-negative floats
+    // (bit order = value order); equal ratios keep the larger period.
+    unsigned long long packed =
+        ((unsigned long long)__float_as_uint(achieved / constraint) << 32) |
+        __float_as_uint(achieved);
+    atomicMax(worst, packed);
   }
 }
 
@@ -276,7 +280,7 @@ struct StaDomainsArgs {
   int32_t K;
   float* arr_all;               // [K * num_blocks]
   float* req_all;               // [K * num_blocks]
-  unsigned* worst_bits;         // [2] device scratch (ratio bits, achieved)
+  unsigned long long* worst_bits;  // [1] device: ratio bits << 32 | achieved
 };
 
 int pnr_sta_analyze_domains(const StaDomainsArgs* d, void* stream) {
@@ -289,7 +293,7 @@ int pnr_sta_analyze_domains(const StaDomainsArgs* d, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const int32_t* ls = a->level_start_host;
   hipError_t me;
-  me = hipMemsetAsync(d->worst_bits, 0, 2 * sizeof(unsigned), st);
+  me = hipMemsetAsync(d->worst_bits, 0, sizeof(unsigned long long), st);
   if (me != hipSuccess) return (int)me;
   // slack sentinel: all-ones encoded bits (= +inf in the ordering);
   // crit zero

@@ -137,12 +137,14 @@ class GpuSTA:
 
     def analyze_domains(self, conn_delay, block_clock, periods):
         """Multi-clock analysis on the device (reference:
-        do_timing_analysis_new's (src,sink)-domain-pair loop;
-        EXPERIMENTAL — pending round-2 GPU validation against the CPU
-        TimingGraph.analyze_domains). Returns (worst_achieved_period,
-        slack[], crit[]); the per-conn slack/crit arrays are exact, the
-        worst-period scalar is tracked with a benign race and should be
-        treated as advisory on the GPU path."""
+        do_timing_analysis_new's (src,sink)-domain-pair loop). Returns
+        (worst_achieved_period, slack[], crit[]), equal to the CPU
+        TimingGraph.analyze_domains bit for bit (crit up to the max_crit
+        clamp; tests/test_sta_exact.py). The worst period is the achieved
+        period of the largest achieved/constraint ratio, tracked as one
+        packed 64-bit max; among equal ratios the larger period wins
+        (the CPU engine keeps the first it meets). With no analysable
+        (source, sink) pair both engines return periods[0]."""
         torch = self.torch
         K = len(periods)
         nb = self.netlist.num_blocks
@@ -156,7 +158,8 @@ class GpuSTA:
                                 device=self.device)
         t_req_all = torch.zeros(K * nb, dtype=torch.float32,
                                 device=self.device)
-        t_worst = torch.zeros(2, dtype=torch.int32, device=self.device)
+        # (ratio bits << 32) | achieved-period bits, see sta_slack_domains
+        t_worst = torch.zeros(1, dtype=torch.int64, device=self.device)
         d = StaDomainsArgs()
         d.base = self._base_args(t_delay)
         pt = lambda t: ct.c_void_p(t.data_ptr())
@@ -167,10 +170,12 @@ class GpuSTA:
         rc = self.lib.pnr_sta_analyze_domains(ct.byref(d), stream)
         hip_api.check(rc, "sta_analyze_domains")
         torch.cuda.synchronize(self.device)
-        worst = float(np.frombuffer(
-            t_worst[1:2].cpu().numpy().tobytes(), dtype=np.float32)[0])
-        if worst == 0.0:
-            worst = float(max(periods))
+        packed = int(t_worst.item())
+        if packed >> 32 == 0:  # no pair analysed (the CPU engine's start)
+            worst = float(np.float32(periods[0]))
+        else:
+            worst = float(np.asarray([packed & 0xFFFFFFFF],
+                                     dtype=np.uint32).view(np.float32)[0])
         return (worst, self.t_slack.cpu().numpy(),
                 self.t_crit.cpu().numpy())
 

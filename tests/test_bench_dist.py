@@ -11,6 +11,14 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 
 
+def _cpu_only_env():
+    """Environment of a bench.py child that must take the CPU engines: two
+    tests below state what those write, also on a machine with a GPU."""
+    env = dict(os.environ)
+    env["HIP_VISIBLE_DEVICES"] = "-1"
+    return env
+
+
 def test_bench_torchrun_world2():
     env = dict(os.environ)
     env["MASTER_ADDR"] = "127.0.0.1"
@@ -71,7 +79,8 @@ def test_bench_dump_outputs_repeat(tmp_path):
             [sys.executable, str(ROOT / "bench.py"), "--gpus", "1",
              "--steps", "1", "--warmup", "0", "--config", "tseng",
              "--fill", "0.3", "--dump-outputs", str(tmp_path / sub)],
-            capture_output=True, text=True, timeout=600, cwd=ROOT)
+            capture_output=True, text=True, timeout=600, cwd=ROOT,
+            env=_cpu_only_env())
         assert r.returncode == 0, r.stderr[-2000:]
     files = sorted((tmp_path / "a").glob("*.npy"))
     assert files
@@ -93,7 +102,8 @@ def test_bench_dump_outputs_and_full(tmp_path):
         [sys.executable, str(ROOT / "bench.py"), "--gpus", "1",
          "--steps", "3", "--warmup", "0", "--config", "tseng",
          "--fill", "0.3", "--full", "--dump-outputs", str(tmp_path / "o")],
-        capture_output=True, text=True, timeout=600, cwd=ROOT)
+        capture_output=True, text=True, timeout=600, cwd=ROOT,
+        env=_cpu_only_env())
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(
         [l for l in r.stdout.splitlines() if l.startswith("{")][-1])

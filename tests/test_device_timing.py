@@ -333,8 +333,10 @@ def test_place_timing_refresh_matches_cpu_sta(name):
     want = np.asarray(c) ** 1.0
     got = p.t_conn_crit.cpu().numpy()
     assert want.max() > 0.99            # unclamped, like the CPU engine
-    assert np.allclose(got, want, rtol=1e-4, atol=1e-5)
-    assert float(t_cpd.item()) == pytest.approx(cpd, rel=1e-5)
+    # cpd to the bit, crit within the reciprocal-vs-division bound
+    # (tests/test_sta_exact.py); exponent 1 is a plain copy
+    assert np.abs(got.astype(np.float64) - want).max() <= 6 * 2.0 ** -24
+    assert np.float32(t_cpd.item()) == np.float32(cpd)
 
 
 # ---- 4. whole anneal: device path equals host path, same engine ----

@@ -1,0 +1,682 @@
+"""GPU STA kernels (csrc/hip/sta_kernel.hip) against exact host models.
+
+Every value the forward, cpd, backward and slack kernels produce is a chain
+of single fp32 `+`, `-`, `max`, `min`, and max/min do not depend on the
+order of their operands. So `t_arr`, `t_req`, `cpd` and `slack` must equal a
+sequential fp32 evaluation bit for bit, the 3.0e38 "unconstrained" entries
+included. Three host oracles:
+
+* `replay32`: a numpy float32 replay of `pnr_sta_analyze`, level by level,
+  over the same `level_arrays()` / `csr_arrays()` that `GpuSTA` uploads. It
+  is checked here, on the CPU, to equal the CPU engine's `cpd` and `slack`
+  bitwise; it is the only oracle for `GpuSTA.t_arr` / `GpuSTA.t_req`, which
+  the CPU engine does not expose.
+* `ref64`: an independent float64 longest-path / required-time computation
+  from the definition (own adjacency from the net arrays, Kahn order over
+  the combinational blocks, no level arrays). It catches an error that both
+  fp32 implementations could share. Bound: an arrival is a chain of at most
+  2L+2 fp32 additions (L levels; one connection and one block delay per
+  level, clock-to-Q, setup) of non-negative terms, every partial sum at most
+  the largest value M in play, so |t32 - t64| <= (2L+2) * 2^-24 * M. For
+  `t_req` and finite `slack` M = cpd (twice the bound for slack, a
+  difference of two such chains); for `t_arr` M = max(cpd, largest arrival),
+  because a block that reaches no flip-flop is not bounded by cpd.
+* multi-domain: the CPU engine itself (`STA.analyze_domains`), one
+  subtraction and one IEEE division per (connection, pair) on both sides.
+
+Only the single-domain `crit` may differ from the CPU engine: the kernel
+multiplies by 1/cpd where the CPU divides. With q = slack/cpd, |q| <= 1
+wherever the clamp does not decide: the reciprocal, the product (absent
+when the compiler fuses it into the subtraction) and the subtraction each
+add at most 2^-24, so |crit - clip(1 - slack/cpd)| <= 4 * 2^-24 with one to
+spare, and <= 6 * 2^-24 against the CPU engine's own fp32 `crit` (its
+division and subtraction add two more).
+
+Measured on an MI355X (docs/MEASUREMENTS.md): `crit` deviates by at most
+0.85 * 2^-24 from the float64 value and 1.13 * 2^-24 from the CPU engine.
+"""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from parallel_eda_amd.arch.archdef import get_arch
+from parallel_eda_amd.io.synth import NetlistPy
+from parallel_eda_amd.timing.sta import STA, block_delays
+
+gpu = pytest.mark.gpu
+
+F = np.float32
+BIG = F(3.0e38)            # the kernels' "unconstrained" value
+EPS = 2.0 ** -24           # half an ulp of 1.0f
+ONE_PASS = 2048 * 256      # threads of one pass of the grid-stride kernels
+DELAYS = ("rand", "zero", "const", "four", "outlier")
+K = 3
+NO_PAIR_PERIODS = np.asarray([3e-9, 5e-9, 2e-9], F)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _same_bits(got, want, what):
+    got, want = _bits(np.atleast_1d(got)), _bits(np.atleast_1d(want))
+    assert got.shape == want.shape, what
+    bad = np.nonzero(got != want)[0]
+    assert len(bad) == 0, f"{what}: {len(bad)} differ, first at {bad[:5]}"
+
+
+# ---------------------------------------------------------------- netlists
+
+def _netlist(nb, drv, snk, block_type, is_seq):
+    """One net per driving block; connections ordered by (driver, sink),
+    duplicates dropped."""
+    key = np.unique(np.asarray(drv, np.int64) * nb + np.asarray(snk, np.int64))
+    drv, snk = key // nb, key % nb
+    assert (drv != snk).all()
+    nets, counts = np.unique(drv, return_counts=True)
+    sptr = np.concatenate([[0], np.cumsum(counts)])
+    return NetlistPy(block_type, is_seq, nets, sptr, snk)
+
+
+def layered(sizes, n_ff, n_orphan, n_dead, seed, fanin32=True):
+    """Layered DAG. Level 0: `n_ff` flip-flops (the first quarter typed as
+    pads) and `n_orphan` combinational blocks without fanin. Level l >= 1:
+    `sizes[l-1]` combinational blocks, each with one driver in level l-1
+    and 0..3 more from any earlier level. Every combinational block without
+    fanout gets a flip-flop sink, except `n_dead` blocks of the last level.
+    A tenth each of the combinational blocks is typed RAM and DSP, which
+    only a heterogeneous arch looks at."""
+    rng = np.random.default_rng(seed)
+    ff = np.arange(n_ff)
+    orphan = n_ff + np.arange(n_orphan)
+    levels = [np.concatenate([ff, orphan])]
+    nb = n_ff + n_orphan
+    drv, snk = [], []
+    for n in sizes:
+        blk = nb + np.arange(n)
+        nb += n
+        drv.append(rng.choice(levels[-1], n))
+        snk.append(blk)
+        extra = rng.integers(0, 4, n)
+        drv.append(rng.choice(np.concatenate(levels), int(extra.sum())))
+        snk.append(np.repeat(blk, extra))
+        levels.append(blk)
+    if fanin32:
+        drv.append(rng.choice(np.concatenate(levels[:-1]), 40, replace=False))
+        snk.append(np.full(40, levels[-1][0]))
+    comb = np.arange(n_ff, nb)
+    has_out = np.zeros(nb, bool)
+    has_out[np.concatenate(drv)] = True
+    dead = levels[-1][len(levels[-1]) - n_dead:]
+    assert not has_out[dead].any()
+    to_ff = comb[~has_out[comb] | (rng.random(len(comb)) < 0.3)]
+    to_ff = np.setdiff1d(to_ff, dead)
+    drv.append(to_ff)
+    snk.append(rng.choice(ff, len(to_ff)))
+    # flip-flop straight into flip-flop
+    drv.append(ff[:8])
+    snk.append(ff[8:16])
+    is_seq = np.zeros(nb, np.uint8)
+    is_seq[ff] = 1
+    block_type = np.ones(nb, np.int8)
+    block_type[ff[: n_ff // 4]] = 0
+    kind = rng.random(nb)
+    block_type[(is_seq == 0) & (kind < 0.1)] = 2
+    block_type[(is_seq == 0) & (kind >= 0.1) & (kind < 0.2)] = 3
+    nl = _netlist(nb, np.concatenate(drv), np.concatenate(snk),
+                  block_type, is_seq)
+    return nl, [len(levels[0])] + list(sizes)
+
+
+CHAIN = 12
+N_SHALLOW = ONE_PASS
+N_DEEP = 41
+
+
+def stride_netlist():
+    """Just over one grid-stride pass of blocks and of connections, both
+    counts odd. Block 0 is a flip-flop, block 1 a combinational block
+    without fanin, blocks 2..13 a combinational chain c1..c12. c1 feeds
+    N_SHALLOW flip-flops, which fill the first pass; c12 feeds the N_DEEP
+    flip-flops behind them. With every delay below 2 ns and 11 block delays
+    of 261 ps between c1 and c12, the critical endpoints are among the
+    last N_DEEP blocks and the connections into them among the last N_DEEP
+    connections whatever the delay vector."""
+    src, orphan, c = 0, 1, 2 + np.arange(CHAIN)
+    first_ff = 2 + CHAIN
+    shallow = first_ff + np.arange(N_SHALLOW)
+    deep = shallow[-1] + 1 + np.arange(N_DEEP)
+    nb = int(deep[-1]) + 1
+    drv = np.concatenate([[src, src, orphan], c[:-1],
+                          np.full(N_SHALLOW, c[0]), np.full(N_DEEP, c[-1])])
+    snk = np.concatenate([[c[0], shallow[0], shallow[0]], c[1:],
+                          shallow, deep])
+    is_seq = np.ones(nb, np.uint8)
+    is_seq[orphan] = 0
+    is_seq[c] = 0
+    return _netlist(nb, drv, snk, np.ones(nb, np.int8), is_seq)
+
+
+def _small(name):
+    if name == "chain":      # the four blocks of test_sta_hand_case
+        return NetlistPy([0, 0, 1, 1], [1, 1, 0, 0], [0, 2, 3],
+                         [0, 1, 2, 3], [2, 3, 1])
+    if name == "noseq":      # no sequential block at all
+        return _netlist(5, [0, 0, 1, 2, 3], [2, 3, 2, 4, 4],
+                        np.ones(5, np.int8), np.zeros(5, np.uint8))
+    if name == "idle_ff":    # flip-flops 1, 5, 6 have no connection into them
+        return _netlist(7, [1, 2, 3, 3, 5], [2, 3, 0, 4, 3],
+                        [0, 0, 1, 1, 1, 1, 1], [1, 1, 0, 0, 1, 1, 1])
+    raise KeyError(name)
+
+
+WIDE_SIZES = [257, 600, 256, 255, 2, 1, 40]
+SINGLE = ("wide", "wide_het", "stride", "chain", "noseq", "idle_ff")
+DOMAIN = ("wide", "wide_het", "mid", "stride")
+
+
+@functools.lru_cache(maxsize=None)
+def _graph(name):
+    if name == "wide":
+        return layered(WIDE_SIZES, n_ff=900, n_orphan=3, n_dead=3, seed=11)
+    if name == "mid":
+        return layered([4000] * 6, n_ff=3000, n_orphan=5, n_dead=5, seed=12)
+    if name == "closed":     # every arrival starts at a flip-flop
+        return layered([70, 300, 40], n_ff=50, n_orphan=0, n_dead=2, seed=13)
+    if name == "stride":
+        return stride_netlist(), None
+    return _small(name), None
+
+
+def delay_vectors(nl, seed):
+    """The five delay vectors of one netlist."""
+    rng = np.random.default_rng(seed)
+    nc = nl.num_conns
+    into_ff = np.nonzero(nl.block_is_seq[nl.net_sinks])[0]
+    at = int(into_ff[-1]) if len(into_ff) else nc - 1
+    outlier = (rng.random(nc) * 2e-9).astype(F)
+    outlier[at] = 1e-6
+    return {
+        "rand": (rng.random(nc) * 2e-9).astype(F),
+        "zero": np.zeros(nc, F),
+        "const": np.full(nc, 0.7e-9, F),          # every max and min ties
+        "four": (rng.integers(0, 4, nc) * 0.25e-9).astype(F),
+        "outlier": outlier,
+    }
+
+
+@functools.lru_cache(maxsize=None)
+def case(name):
+    graph = "wide" if name == "wide_het" else name
+    nl, sizes = _graph(graph)
+    arch = get_arch("tiny_het" if name == "wide_het" else "tiny")
+    sta = STA(nl, arch)
+    return SimpleNamespace(name=name, nl=nl, arch=arch, sta=sta, sizes=sizes,
+                           L=sta.num_levels,
+                           delays=delay_vectors(nl, seed=len(name)))
+
+
+# ------------------------------------------------------------ host oracles
+
+def _ragged(ptr, rows):
+    """Positions ptr[r]..ptr[r+1] of every r in rows, concatenated, and for
+    each the position of its r in rows."""
+    lo = ptr[rows]
+    n = ptr[rows + 1] - lo
+    own = np.repeat(np.arange(len(rows)), n)
+    off = np.arange(int(n.sum())) - np.repeat(np.cumsum(n) - n, n)
+    return lo[own] + off, own
+
+
+def _consts(nl, arch):
+    bd = block_delays(nl, arch)
+    if bd is None:
+        bd = np.full(nl.num_blocks, arch.T_clb, F)
+    return bd.astype(F), F(arch.T_seq_out), F(arch.T_seq_in)
+
+
+def replay32(nl, arch, delay, tg=None):
+    """pnr_sta_analyze in numpy float32: forward level by level, cpd,
+    backward level by level, slack. Returns t_arr, t_req, cpd, slack (and
+    the per-block endpoint arrival the cpd is the maximum of)."""
+    tg = tg or STA(nl, arch).tg
+    blocks, start = tg.level_arrays()
+    in_ptr, in_conn, out_ptr, out_conn, drv = tg.csr_arrays()
+    snk = nl.net_sinks
+    seq = nl.block_is_seq.astype(bool)
+    bd, t_out, t_in = _consts(nl, arch)
+    delay = np.ascontiguousarray(delay, F)
+    nb = nl.num_blocks
+
+    def in_arrival(rows):
+        k, own = _ragged(in_ptr, rows)
+        c = in_conn[k]
+        a = np.zeros(len(rows), F)
+        np.maximum.at(a, own, t_arr[drv[c]] + delay[c])
+        return a
+
+    t_arr = np.zeros(nb, F)
+    for lv in range(len(start) - 1):
+        b = blocks[start[lv]:start[lv + 1]]
+        t_arr[b[seq[b]]] = t_out
+        comb = b[~seq[b]]
+        t_arr[comb] = in_arrival(comb) + bd[comb]
+    endpoint = np.zeros(nb, F)
+    ends = np.nonzero(seq)[0]
+    endpoint[ends] = in_arrival(ends) + t_in
+    cpd = endpoint.max() if len(ends) else F(0)
+    if cpd <= 0:
+        cpd = F(1e-12)      # the CPU engine's floor; the kernels keep 0
+
+    def req_in(c):
+        s = snk[c]
+        return np.where(seq[s], cpd - t_in, t_req[s] - bd[s]).astype(F)
+
+    t_req = np.full(nb, BIG, F)
+    for lv in range(len(start) - 2, -1, -1):
+        b = blocks[start[lv]:start[lv + 1]]
+        k, own = _ragged(out_ptr, b)
+        c = out_conn[k]
+        r = np.full(len(b), BIG, F)
+        np.minimum.at(r, own, req_in(c) - delay[c])
+        t_req[b] = r
+    every = np.arange(nl.num_conns)
+    slack = req_in(every) - (t_arr[drv] + delay)
+    assert slack.dtype == F and t_arr.dtype == F and t_req.dtype == F
+    return SimpleNamespace(t_arr=t_arr, t_req=t_req, cpd=F(cpd), slack=slack,
+                           endpoint=endpoint)
+
+
+def ref64(nl, arch, delay):
+    """Longest path and required time in float64, from the definition:
+    t_arr[ff] = T_seq_out, t_arr[comb] = max(0, max_in(t_arr[drv] + d)) +
+    delay(comb); cpd = max over flip-flops of max_in + T_seq_in; t_req[b] =
+    min over fanout of (cpd - T_seq_in | t_req[snk] - delay(snk)) - d,
+    +inf without fanout. Own adjacency, Kahn order over the combinational
+    blocks; the inputs are the same fp32 numbers, widened."""
+    nb = nl.num_blocks
+    drv = np.repeat(nl.net_driver, np.diff(nl.net_sink_ptr)).astype(np.int64)
+    snk = nl.net_sinks.astype(np.int64)
+    seq = nl.block_is_seq.astype(bool)
+    bd, t_out, t_in = (np.float64(x) for x in _consts(nl, arch))
+    d = np.asarray(delay, F).astype(np.float64)
+
+    by_snk = np.argsort(snk, kind="stable")
+    in_ptr = np.concatenate([[0], np.cumsum(np.bincount(snk, minlength=nb))])
+    by_drv = np.argsort(drv, kind="stable")
+    out_ptr = np.concatenate([[0], np.cumsum(np.bincount(drv, minlength=nb))])
+
+    def fanin(b):
+        return by_snk[in_ptr[b]:in_ptr[b + 1]]
+
+    def fanout(b):
+        return by_drv[out_ptr[b]:out_ptr[b + 1]]
+
+    pend = np.bincount(snk[~seq[drv] & ~seq[snk]], minlength=nb)
+    order = [b for b in np.nonzero(~seq)[0] if pend[b] == 0]
+    for b in order:                      # grows while it is walked
+        s = snk[fanout(b)]
+        for s in s[~seq[s]]:
+            pend[s] -= 1
+            if pend[s] == 0:
+                order.append(s)
+    assert len(order) == int((~seq).sum())
+
+    t_arr = np.where(seq, t_out, 0.0)
+    for b in order:
+        c = fanin(b)
+        t_arr[b] = max(0.0, (t_arr[drv[c]] + d[c]).max(initial=0.0)) + bd[b]
+    at_in = np.zeros(nb)
+    np.maximum.at(at_in, snk, t_arr[drv] + d)
+    cpd = (at_in[seq] + t_in).max() if seq.any() else 0.0
+
+    t_req = np.full(nb, np.inf)
+
+    def req_in(c):
+        s = snk[c]
+        return np.where(seq[s], cpd - t_in, t_req[s] - bd[s])
+
+    for b in order[::-1]:
+        c = fanout(b)
+        t_req[b] = (req_in(c) - d[c]).min(initial=np.inf)
+    ffs = seq[drv]
+    np.minimum.at(t_req, drv[ffs], req_in(np.nonzero(ffs)[0]) - d[ffs])
+    every = np.arange(len(snk))
+    return SimpleNamespace(t_arr=t_arr, t_req=t_req, cpd=cpd,
+                           slack=req_in(every) - (t_arr[drv] + d))
+
+
+@functools.lru_cache(maxsize=None)
+def oracle(name, dname):
+    cs = case(name)
+    return replay32(cs.nl, cs.arch, cs.delays[dname], cs.sta.tg)
+
+
+@functools.lru_cache(maxsize=None)
+def cpu_engine(name, dname):
+    cs = case(name)
+    return cs.sta.analyze(cs.delays[dname])
+
+
+def crit64(slack, cpd, max_crit):
+    """clip(1 - slack/cpd, 0, max_crit) in float64 from the fp32 values."""
+    q = slack.astype(np.float64) / max(float(cpd), float(F(1e-12)))
+    return np.clip(1.0 - q, 0.0, float(F(max_crit)))
+
+
+@functools.lru_cache(maxsize=None)
+def domains(name):
+    """Three-domain set-up of one netlist and the CPU engine's answer.
+    Periods are 0.55, 1.0 and 1.6 times the single-domain cpd, so the
+    first domain is violated and the last has room. `top` is the set of
+    achieved periods among the (connection, pair) entries with the largest
+    achieved/constraint, rebuilt from one CPU run per pair."""
+    cs = case(name)
+    nl = cs.nl
+    d = cs.delays["rand"]
+    seq = nl.block_is_seq.astype(bool)
+    bc = np.where(seq, np.arange(nl.num_blocks) % K, -1).astype(np.int32)
+    periods = (np.asarray([0.55, 1.0, 1.6]) * oracle(name, "rand").cpd
+               ).astype(F)
+    wp, slack, crit = cs.sta.analyze_domains(d, bc, periods)
+    best, top, reached_any = F(-1), set(), np.zeros(nl.num_conns, bool)
+    for ci in range(K):
+        for cj in range(K):
+            skip = np.ones((K, K), np.uint8)
+            skip[ci, cj] = 0
+            _, s, cr = cs.sta.analyze_domains(d, bc, periods, pair_skip=skip)
+            reached = ~((s == 0) & (cr == 0))
+            reached_any |= reached
+            if not reached.any():
+                continue
+            achieved = periods[cj] - s[reached]
+            ratio = achieved / periods[cj]
+            assert ratio.dtype == F
+            if ratio.max() > best:
+                best, top = ratio.max(), set()
+            if ratio.max() == best:
+                top |= set(achieved[ratio == best].tolist())
+    return SimpleNamespace(d=d, bc=bc, periods=periods, wp=wp, slack=slack,
+                           crit=crit, top=top, reached=reached_any)
+
+
+# ------------------------------------------------- CPU: oracle self-checks
+
+@pytest.mark.parametrize("name", SINGLE + ("mid", "closed"))
+def test_replay32_equals_cpu_engine(name):
+    for dname in DELAYS:
+        cpd, slack, _ = cpu_engine(name, dname)
+        ref = oracle(name, dname)
+        _same_bits(ref.cpd, F(cpd), f"{name}/{dname} cpd")
+        _same_bits(ref.slack, slack, f"{name}/{dname} slack")
+
+
+@pytest.mark.parametrize("name", SINGLE + ("closed",))
+def test_ref64_within_bound(name):
+    cs = case(name)
+    for dname in DELAYS:
+        r32, r64 = oracle(name, dname), ref64(cs.nl, cs.arch, cs.delays[dname])
+        bound = (2 * cs.L + 2) * EPS * r64.cpd
+        if cs.nl.block_is_seq.any():
+            assert abs(float(r32.cpd) - r64.cpd) <= bound
+        else:
+            assert r64.cpd == 0 and r32.cpd == F(1e-12)
+        top = max(r64.cpd, r64.t_arr.max())
+        assert np.abs(r32.t_arr - r64.t_arr).max() <= (2 * cs.L + 2) * EPS * top
+        # unconstrained in one is unconstrained in the other, and exactly so
+        for v32, v64, mult in ((r32.t_req, r64.t_req, 1),
+                               (r32.slack, r64.slack, 2)):
+            free = np.isinf(v64)
+            assert np.array_equal(v32[free], np.full(free.sum(), BIG))
+            if (~free).any():
+                err = np.abs(v32[~free] - v64[~free]).max()
+                assert err <= mult * bound, (name, dname, err / bound)
+                assert v32[~free].max() < 1e30
+
+
+def test_case_wide():
+    for name in ("wide", "wide_het"):
+        cs = case(name)
+        nl = cs.nl
+        _, start = cs.sta.tg.level_arrays()
+        counts = np.diff(start).tolist()
+        assert counts == cs.sizes
+        assert {1, 2, 255, 256, 257} <= set(counts) and max(counts) > 512
+        assert 2000 < nl.num_blocks < 10000
+        seq = nl.block_is_seq.astype(bool)
+        drv = np.repeat(nl.net_driver, np.diff(nl.net_sink_ptr))
+        fanin = np.bincount(nl.net_sinks, minlength=nl.num_blocks)
+        fanout = np.bincount(drv, minlength=nl.num_blocks)
+        assert (~seq & (fanout == 0)).any() and (~seq & (fanin == 0)).any()
+        assert (seq[drv] & seq[nl.net_sinks]).any()
+        assert fanin[~seq].max() >= 32
+        for dname in DELAYS:
+            slack = oracle(name, dname).slack
+            free = slack == BIG
+            assert 0 < free.sum() and 2 * free.sum() <= nl.num_conns
+            assert slack[~free].max() < 1e30
+    assert block_delays(case("wide").nl, case("wide").arch) is None
+    bd = block_delays(case("wide_het").nl, case("wide_het").arch)
+    assert bd is not None and len(np.unique(bd)) >= 2
+    assert case("wide").nl is case("wide_het").nl
+
+
+def test_case_stride():
+    cs = case("stride")
+    nl = cs.nl
+    assert nl.num_blocks > ONE_PASS and nl.num_blocks % 2 == 1
+    assert nl.num_conns > ONE_PASS and nl.num_conns % 2 == 1
+    assert nl.num_blocks < ONE_PASS + 64 and nl.num_conns < ONE_PASS + 64
+    for dname in DELAYS:
+        ref = oracle("stride", dname)
+        ends = np.nonzero(ref.endpoint == ref.cpd)[0]
+        assert len(ends) and ends.min() > ONE_PASS, dname
+        # the connections into them carry the minimum slack of all
+        # connections into flip-flops (the chain before them has the same
+        # slack up to rounding), far below the first pass's flip-flops
+        into = np.nonzero(np.isin(nl.net_sinks, ends))[0]
+        assert into.min() > ONE_PASS
+        into_ff = nl.block_is_seq[nl.net_sinks] > 0
+        assert (ref.slack[into] == ref.slack[into_ff].min()).all()
+        first = into_ff & (nl.net_sinks < 2 + CHAIN + N_SHALLOW)
+        assert first.sum() > ONE_PASS
+        assert ref.slack[first].min() > 1e-10 > abs(ref.slack.min())
+
+
+def test_case_degenerate():
+    cs = case("noseq")
+    assert not cs.nl.block_is_seq.any()
+    for dname in DELAYS:
+        cpd, slack, crit = cpu_engine("noseq", dname)
+        assert F(cpd) == F(1e-12)
+        assert (slack == BIG).all() and (crit == 0).all()
+    cs = case("idle_ff")
+    fanin = np.bincount(cs.nl.net_sinks, minlength=cs.nl.num_blocks)
+    assert ((fanin == 0) & (cs.nl.block_is_seq > 0)).sum() == 3
+    cs = case("chain")
+    cpd, slack, crit = cs.sta.analyze(np.full(3, 1e-9, F))
+    a = cs.arch
+    assert cpd == pytest.approx(a.T_seq_out + 3e-9 + 2 * a.T_clb + a.T_seq_in,
+                                rel=1e-6)
+
+
+@pytest.mark.parametrize("name", DOMAIN)
+def test_case_domains(name):
+    cs, dm = case(name), domains(name)
+    seq = cs.nl.block_is_seq.astype(bool)
+    for k in range(K):
+        assert (dm.bc[seq] == k).any()
+    assert (dm.bc[~seq] == -1).all()
+    assert (dm.slack < 0).any() and (dm.slack > 0).any()
+    # a connection no pair reaches: the sentinel, slack 0 and crit 0
+    assert (~dm.reached).any()
+    assert (dm.slack[~dm.reached] == 0).all()
+    assert (dm.crit[~dm.reached] == 0).all()
+    # one worst achieved/constraint, in the sense that decides the result:
+    # every entry with the largest ratio has the same achieved period (the
+    # connections of one critical path share it), so "first met" (CPU) and
+    # "largest period" (GPU) name the same number
+    assert len(dm.top) == 1 and F(dm.wp) == F(dm.top.pop())
+    if name in ("mid", "stride"):
+        assert cs.nl.num_conns * K * K > ONE_PASS
+    if name == "stride":
+        assert cs.nl.num_conns > ONE_PASS      # finish kernel strides too
+
+
+def test_case_k1_and_no_pair():
+    cs = case("closed")
+    nl = cs.nl
+    seq = nl.block_is_seq.astype(bool)
+    fanin = np.bincount(nl.net_sinks, minlength=nl.num_blocks)
+    assert (fanin[~seq] > 0).all()
+    ref = oracle("closed", "rand")
+    assert (ref.slack == BIG).any()
+    wp, slack, crit = cs.sta.analyze_domains(
+        cs.delays["rand"], np.where(seq, 0, -1), [ref.cpd])
+    _same_bits(slack, np.where(ref.slack == BIG, F(0), ref.slack), "K=1 slack")
+    # no analysable pair: the CPU engine answers periods[0], not the maximum
+    wp, slack, crit = cs.sta.analyze_domains(
+        cs.delays["rand"], np.full(nl.num_blocks, -1), NO_PAIR_PERIODS)
+    assert F(wp) == NO_PAIR_PERIODS[0] != NO_PAIR_PERIODS.max()
+    assert (slack == 0).all() and (crit == 0).all()
+
+
+# ------------------------------------------------------- GPU: single domain
+
+def _gsta(cs, max_crit):
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    return GpuSTA(cs.nl, cs.arch, max_crit=max_crit)
+
+
+def _check_single(cs, gs, dname, got, worst):
+    cpd, slack, crit = got
+    name = cs.name
+    ref = oracle(name, dname)
+    tag = f"{name}/{dname}/max_crit={gs.max_crit}"
+    if cs.nl.block_is_seq.any():
+        _same_bits(F(cpd), ref.cpd, f"{tag} cpd")
+    else:
+        assert 0 <= cpd <= 1e-12, tag    # the CPU engine floors at 1e-12
+    _same_bits(gs.t_arr.cpu().numpy(), ref.t_arr, f"{tag} t_arr")
+    _same_bits(gs.t_req.cpu().numpy(), ref.t_req, f"{tag} t_req")
+    _same_bits(slack, ref.slack, f"{tag} slack")
+    _same_bits(slack, cpu_engine(name, dname)[1], f"{tag} slack vs CPU")
+    cap = F(gs.max_crit)
+    assert not np.isnan(crit).any(), tag
+    assert (crit >= 0).all() and (crit <= cap).all(), tag
+    assert (crit[ref.slack == BIG] == 0).all(), tag
+    e64 = np.abs(crit - crit64(ref.slack, ref.cpd, gs.max_crit)).max() / EPS
+    ecpu = np.abs(crit.astype(np.float64) -
+                  np.minimum(cpu_engine(name, dname)[2], cap)).max() / EPS
+    worst[0], worst[1] = max(worst[0], e64), max(worst[1], ecpu)
+    assert e64 <= 4 and ecpu <= 6, (tag, e64, ecpu)
+
+
+@gpu
+@pytest.mark.parametrize("name", SINGLE)
+def test_gpu_single_domain_exact(name):
+    cs = case(name)
+    worst = [0.0, 0.0]
+    for max_crit in (1.0, 0.99):
+        gs = _gsta(cs, max_crit)
+        for dname in DELAYS:
+            _check_single(cs, gs, dname, gs.analyze(cs.delays[dname]), worst)
+    print(f"{name}: max |crit - float64| = {worst[0]:.3f} * 2^-24, "
+          f"max |crit - CPU engine| = {worst[1]:.3f} * 2^-24")
+
+
+def _poison(gs):
+    for t in (gs.t_arr, gs.t_req, gs.t_slack, gs.t_crit):
+        t.fill_(float("nan"))
+
+
+@gpu
+@pytest.mark.parametrize("name", ("wide_het", "idle_ff"))
+def test_gpu_state_reuse(name):
+    cs = case(name)
+    dm = domains(name) if name == "wide_het" else None
+    d1, d2 = cs.delays["rand"], cs.delays["outlier"]
+    gs = _gsta(cs, 1.0)
+    worst = [0.0, 0.0]
+
+    def snap(res):
+        return (F(res[0]), res[1].copy(), res[2].copy(),
+                gs.t_arr.cpu().numpy(), gs.t_req.cpu().numpy())
+
+    first = snap(gs.analyze(d1))
+    if name == "wide_het":
+        gs.analyze_domains(dm.d, dm.bc, dm.periods)
+    else:
+        seq = cs.nl.block_is_seq > 0
+        gs.analyze_domains(d2, np.where(seq, 0, -1), [2e-9])
+    third = snap(gs.analyze(d1))
+    for a, b, what in zip(first, third, ("cpd", "slack", "crit", "t_arr",
+                                         "t_req")):
+        _same_bits(b, a, f"{name} {what} after analyze_domains")
+    second = snap(gs.analyze(d2))
+    fresh_gs = _gsta(cs, 1.0)
+    fresh = fresh_gs.analyze(d2)
+    fresh = (F(fresh[0]), fresh[1], fresh[2], fresh_gs.t_arr.cpu().numpy(),
+             fresh_gs.t_req.cpu().numpy())
+    for a, b, what in zip(fresh, second, ("cpd", "slack", "crit", "t_arr",
+                                          "t_req")):
+        _same_bits(b, a, f"{name} {what} of analyze(d2) after analyze(d1)")
+    # NaN in every reused buffer before a call: none may survive
+    _poison(gs)
+    _check_single(cs, gs, "rand", gs.analyze(d1), worst)
+    for t in (gs.t_arr, gs.t_req, gs.t_slack, gs.t_crit):
+        assert not bool(t.isnan().any())
+    if name == "wide_het":
+        _poison(gs)
+        wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
+        assert not np.isnan(slack).any() and not np.isnan(crit).any()
+        _same_bits(slack, dm.slack, "domain slack after NaN prefill")
+        _same_bits(crit, dm.crit, "domain crit after NaN prefill")
+        _same_bits(F(wp), F(dm.wp), "worst period after NaN prefill")
+
+
+# -------------------------------------------------------- GPU: multi-domain
+
+@gpu
+@pytest.mark.parametrize("name", DOMAIN)
+def test_gpu_domains_exact(name):
+    cs, dm = case(name), domains(name)
+    for max_crit in (1.0, 0.99):
+        gs = _gsta(cs, max_crit)
+        for rep in range(2):     # the second call reuses slack/crit
+            wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
+            tag = f"{name}/max_crit={max_crit}/call {rep}"
+            _same_bits(slack, dm.slack, f"{tag} slack")
+            _same_bits(crit, np.minimum(dm.crit, F(max_crit)), f"{tag} crit")
+            _same_bits(F(wp), F(dm.wp), f"{tag} worst period")
+
+
+@gpu
+def test_gpu_domains_no_pair_and_k1():
+    cs = case("closed")
+    nl = cs.nl
+    seq = nl.block_is_seq.astype(bool)
+    d = cs.delays["rand"]
+    gs = _gsta(cs, 1.0)
+    none = np.full(nl.num_blocks, -1)
+    wp_c, sl_c, cr_c = cs.sta.analyze_domains(d, none, NO_PAIR_PERIODS)
+    wp, slack, crit = gs.analyze_domains(d, none, NO_PAIR_PERIODS)
+    _same_bits(F(wp), F(wp_c), "worst period without an analysable pair")
+    assert F(wp) == NO_PAIR_PERIODS[0]
+    _same_bits(slack, sl_c, "slack without an analysable pair")
+    _same_bits(crit, cr_c, "crit without an analysable pair")
+    # K = 1 with period = cpd is the single-domain analysis
+    ref = oracle("closed", "rand")
+    one = np.where(seq, 0, -1)
+    wp_c, sl_c, cr_c = cs.sta.analyze_domains(d, one, [ref.cpd])
+    wp, slack, crit = gs.analyze_domains(d, one, [ref.cpd])
+    _same_bits(slack, np.where(ref.slack == BIG, F(0), ref.slack),
+               "K=1 slack vs replay32")
+    _same_bits(slack, sl_c, "K=1 slack")
+    _same_bits(crit, cr_c, "K=1 crit")
+    _same_bits(F(wp), F(wp_c), "K=1 worst period")
+    # the critical path achieves the period it was given, to rounding
+    # (its slack is a difference of two chains: twice the arrival bound)
+    assert abs(wp - float(ref.cpd)) <= 2 * (2 * cs.L + 2) * EPS * float(ref.cpd)
