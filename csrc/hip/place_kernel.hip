@@ -2,15 +2,26 @@
 //
 // Re-designs the reference's serial try_swap loop (vpr/SRC/place/place.c:1252
 // try_swap, update_bb:2292, get_net_cost:2204, comp_delta_td_cost) as
-// batched parallel moves: each thread proposes one range-limited move/swap,
-// evaluates the EXACT bb+timing delta against the frozen pre-batch state,
-// runs Metropolis, then claims its touched nets + grid locations with
-// atomicMin (move-index priority => deterministic winner set); a second
-// kernel applies the conflict-free winners, whose deltas are exact and
-// additive (disjoint nets/locations => sequential-equivalent batch).
-// Two drivers run the same batch: pnr_place_batch (reset, propose,
-// resolve, apply: four launches, kept as the oracle) and pnr_place_run
-// (propose + commit with epoch-key claims, many batches per call).
+// batches of parallel moves. One batch is three phases, one wavefront per
+// move in each:
+//   propose  lane 0 draws a range-limited move, swap or carry-chain shift;
+//            the wave evaluates the EXACT bb+timing delta against the
+//            frozen pre-batch state, runs Metropolis, records an accepted
+//            move in mv_* and claims its nets and tiles;
+//   resolve  a move wins if it holds every claim it took. Priority is the
+//            move index, so the winner set is deterministic;
+//   apply    winners refresh their nets' cached costs and commit grid and
+//            positions. Winners touch disjoint nets and tiles, so their
+//            deltas are exact and additive: a sequential-equivalent batch.
+// Each phase exists once (propose_move, resolve_move, apply_move). Two
+// drivers run it and must agree to the bit (tests/test_gpu_place_run.py):
+//   pnr_place_batch  reset, propose, resolve, apply: four launches, stop
+//                    rule on the host, MinClaims. Kept as the oracle.
+//   pnr_place_run    propose, then resolve + apply fused into one commit
+//                    launch; stop rule on the device, EpochClaims (no
+//                    reset); many batches per call.
+// They differ in the claim policy, the launches and the stop rule only
+// (docs/KERNELS.md, placer section).
 #include "pnr_hip.h"
 
 namespace pnrh {
@@ -53,28 +64,35 @@ struct PlaceDev {
 
 struct MovesDev {
   int32_t* mv_blk;      // proposer's block
-  int32_t* mv_to;       // encoded dest (x*gy+y)*cap+slot
-  int32_t* mv_other;    // block swapped with (or -1)
+  int32_t* mv_to;       // encoded dest (x*gy+y)*cap+slot; macro: see below
+  int32_t* mv_other;    // block swapped with, -1 = none, -2 - mid = macro
   float* mv_dbb;        // exact bb delta
   float* mv_dtd;        // exact td delta
   uint8_t* mv_flags;    // 1 = Metropolis-accepted candidate; 2 = winner
-  int32_t* net_claim;   // [num_nets] atomicMin move index
-  int32_t* loc_claim;   // [gx*gy] atomicMin move index (tile granularity)
-  int32_t* counters;    // [4]: attempts, accepted, winners, conflicts
+  int32_t* net_claim;   // [num_nets] MinClaims words (pnr_place_batch)
+  int32_t* loc_claim;   // [gx*gy] the same, tile granularity
+  int32_t* counters;    // [4]: attempts, accepted, winners, conflicts, over
+                        // all batches of a run_batches call (host zeroes)
   int32_t n_moves;
 };
+
+// what one batch's propose is run with
+struct Sched {
+  float T; int rlim; float timing_tradeoff, inv_bb_norm, inv_td_norm;
+  uint32_t seed, batch;
+};
+
+#define PROP_WAVES 4
+
+// one wave64 per move, PROP_WAVES waves per workgroup
+__device__ __forceinline__ int move_index() {
+  return blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
+}
 
 __device__ __forceinline__ uint32_t rng_hash(uint32_t a, uint32_t b, uint32_t c) {
   uint32_t h = a * 0x9E3779B9u ^ b * 0x85EBCA6Bu ^ c * 0xC2B2AE35u;
   h ^= h >> 16; h *= 0x7FEB352Du; h ^= h >> 15; h *= 0x846CA68Bu; h ^= h >> 16;
   return h;
-}
-
-__device__ __forceinline__ float cross_count_dev(int n) {
-  const float q3 = 1.0f, q50 = 2.79f;
-  if (n <= 3) return q3;
-  if (n >= 50) return q50 + 0.02616f * (n - 50);
-  return q3 + (q50 - q3) * (n - 3) / 47.0f;
 }
 
 __device__ __forceinline__ bool is_io_loc(const PlaceDev& p, int x, int y) {
@@ -87,80 +105,59 @@ __device__ __forceinline__ int cap_at(const PlaceDev& p, int x, int y) {
   return 0;
 }
 
-// bb cost of net n with up to 2 positional overrides
-__device__ float net_bb_cost(const PlaceDev& p, int n, int32_t b1, int x1,
-                             int y1, int32_t b2, int x2, int y2) {
+// ---- where block b would be after a move: the position overrides ----
+// SwapPos: up to two blocks placed elsewhere (move or swap; -1 = no block)
+struct SwapPos {
+  int32_t b1; int x1, y1; int32_t b2; int x2, y2;
+  __device__ __forceinline__ void operator()(
+      const PlaceDev&, int32_t b, int& x, int& y) const {
+    if (b == b1) { x = x1; y = y1; }
+    else if (b == b2) { x = x2; y = y2; }
+  }
+};
+// every member of macro `mid` displaced by (ddx, ddy)
+struct MacroPos {
+  int mid, ddx, ddy;
+  __device__ __forceinline__ void operator()(
+      const PlaceDev& p, int32_t b, int& x, int& y) const {
+    if (p.macro_of[b] == mid) { x += ddx; y += ddy; }
+  }
+};
+
+// bb cost of net n with its members at `pos`
+template <class Pos> __device__ __forceinline__
+float net_bb_cost(const PlaceDev& p, int n, const Pos& pos) {
   int xmin = 1 << 28, xmax = -1, ymin = 1 << 28, ymax = -1;
   int32_t e0 = p.net_blk_ptr[n], e1 = p.net_blk_ptr[n + 1];
   for (int32_t e = e0; e < e1; ++e) {
     int32_t b = p.net_blks[e];
     int x = p.bx[b], y = p.by[b];
-    if (b == b1) { x = x1; y = y1; }
-    else if (b == b2) { x = x2; y = y2; }
+    pos(p, b, x, y);
     xmin = min(xmin, x); xmax = max(xmax, x);
     ymin = min(ymin, y); ymax = max(ymax, y);
   }
   return p.net_q[n] * ((xmax - xmin + 1) + (ymax - ymin + 1));
 }
 
-// bb cost of net n with every member of macro `mid` displaced (ddx,ddy)
-__device__ float net_bb_cost_macro(const PlaceDev& p, int n, int mid,
-                                   int ddx, int ddy) {
-  int xmin = 1 << 28, xmax = -1, ymin = 1 << 28, ymax = -1;
-  int32_t e0 = p.net_blk_ptr[n], e1 = p.net_blk_ptr[n + 1];
-  for (int32_t e = e0; e < e1; ++e) {
-    int32_t b = p.net_blks[e];
-    int x = p.bx[b], y = p.by[b];
-    if (p.macro_of[b] == mid) { x += ddx; y += ddy; }
-    xmin = min(xmin, x); xmax = max(xmax, x);
-    ymin = min(ymin, y); ymax = max(ymax, y);
-  }
-  return p.net_q[n] * ((xmax - xmin + 1) + (ymax - ymin + 1));
-}
-
-__device__ float net_td_cost_macro(const PlaceDev& p, int n, int mid,
-                                   int ddx, int ddy) {
+// timing cost of net n (sum over conns of crit * delay), members at `pos`
+template <class Pos> __device__ __forceinline__
+float net_td_cost(const PlaceDev& p, int n, const Pos& pos) {
   if (p.delay_mat == nullptr) return 0.0f;
   int32_t e0 = p.net_blk_ptr[n], e1 = p.net_blk_ptr[n + 1];
   int32_t drv = p.net_blks[e0];
   int dx0 = p.bx[drv], dy0 = p.by[drv];
-  if (p.macro_of[drv] == mid) { dx0 += ddx; dy0 += ddy; }
+  pos(p, drv, dx0, dy0);
   float t = 0.0f;
   int32_t c0 = p.net_sink_ptr[n];
   for (int32_t e = e0 + 1; e < e1; ++e) {
     int32_t b = p.net_blks[e];
     int x = p.bx[b], y = p.by[b];
-    if (p.macro_of[b] == mid) { x += ddx; y += ddy; }
+    pos(p, b, x, y);
     int dx = abs(x - dx0), dy = abs(y - dy0);
     t += p.conn_crit[c0 + (e - e0 - 1)] * p.delay_mat[dx * p.gy + dy];
   }
   return t;
 }
-
-// timing cost of net n (sum over conns of crit * delay) with overrides
-__device__ float net_td_cost(const PlaceDev& p, int n, int32_t b1, int x1,
-                             int y1, int32_t b2, int x2, int y2) {
-  if (p.delay_mat == nullptr) return 0.0f;
-  int32_t e0 = p.net_blk_ptr[n], e1 = p.net_blk_ptr[n + 1];
-  int32_t drv = p.net_blks[e0];
-  int dx0 = p.bx[drv], dy0 = p.by[drv];
-  if (drv == b1) { dx0 = x1; dy0 = y1; }
-  else if (drv == b2) { dx0 = x2; dy0 = y2; }
-  float t = 0.0f;
-  int32_t c0 = p.net_sink_ptr[n];
-  for (int32_t e = e0 + 1; e < e1; ++e) {
-    int32_t b = p.net_blks[e];
-    int x = p.bx[b], y = p.by[b];
-    if (b == b1) { x = x1; y = y1; }
-    else if (b == b2) { x = x2; y = y2; }
-    int dx = abs(x - dx0), dy = abs(y - dy0);
-    t += p.conn_crit[c0 + (e - e0 - 1)] * p.delay_mat[dx * p.gy + dy];
-  }
-  return t;
-}
-
-#define MAX_MOVE_NETS 160
-#define PROP_WAVES 4
 
 __device__ __forceinline__ float wave_sum_f32(float v) {
   for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
@@ -168,8 +165,8 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 }
 
 // binary search in block b's sorted net list
-__device__ __forceinline__ bool blk_has_net(const PlaceDev& p, int32_t b,
-                                            int32_t n) {
+__device__ __forceinline__
+bool blk_has_net(const PlaceDev& p, int32_t b, int32_t n) {
   int32_t lo = p.blk_net_ptr[b], hi = p.blk_net_ptr[b + 1];
   while (lo < hi) {
     int32_t mid2 = (lo + hi) >> 1;
@@ -178,182 +175,57 @@ __device__ __forceinline__ bool blk_has_net(const PlaceDev& p, int32_t b,
   return lo < p.blk_net_ptr[b + 1] && p.blk_nets[lo] == n;
 }
 
-__device__ int propose_select_impl(const PlaceDev& p, int rlim,
-                                   uint32_t seed, uint32_t batch, int i,
-                                   int& x1o, int& y1o, int& slot1o);
-
-// One WAVEFRONT per proposal (the per-thread version left ~1 live
-// thread per CU and propose was 52% of LU32 kernel time at 158 us per
-// 554-move batch): lane 0 selects the candidate, the wave evaluates the
-// affected nets' exact deltas in parallel and reduces them, and claims
-// go out lane-strided (atomicMin is idempotent, so the two block lists
-// need no dedup — only the delta sum skips shared nets).
-__launch_bounds__(64 * PROP_WAVES, 2)
-__global__ void place_propose_kernel(PlaceDev p, MovesDev m, float T,
-                                     int rlim, float timing_tradeoff,
-                                     float inv_bb_norm, float inv_td_norm,
-                                     uint32_t seed, uint32_t batch) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
-  if (i >= m.n_moves) return;
-  int sel = -1, sx1 = -1, sy1 = -1, sslot = 0;
-  if (lane == 0) {
-    m.mv_flags[i] = 0;
-    sel = propose_select_impl(p, rlim, seed, batch, i, sx1, sy1, sslot);
-  }
-  sel = __shfl(sel, 0);
-  if (sel < 0) return;
-  const int x1 = __shfl(sx1, 0);
-  const int y1 = __shfl(sy1, 0);
-  const int slot1 = __shfl(sslot, 0);
-  const int32_t blk = sel;
-  const int x0 = p.bx[blk], y0 = p.by[blk];
-  const int mid = p.macro_of ? p.macro_of[blk] : -1;
-  if (mid >= 0) {
-    // -------- macro move (reference: place_macro.c; free-target) -----
-    const int ddx = x1 - x0, ddy = y1 - y0;
-    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
-    if (mm1 - mm0 > 16) return;
-    int ok = 0;
-    if (lane == 0) {
-      ok = 1;
-      for (int32_t j = mm0; j < mm1 && ok; ++j) {
-        int32_t b = p.macro_blk[j];
-        int sx = p.bx[b], sy = p.by[b];
-        int tx = sx + ddx, ty = sy + ddy;
-        if (p.fixed && p.fixed[b]) ok = 0;
-        else if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) ok = 0;
-        else if (p.rx0 >= 0 && (tx < p.rx0 || tx > p.rx1 ||
-                                sx < p.rx0 || sx > p.rx1)) ok = 0;
-        else if (p.tile_btype
-                     ? (p.tile_btype[tx * p.gy + ty] != p.blk_type[b])
-                     : (is_io_loc(p, tx, ty) != (p.blk_type[b] == 0))) ok = 0;
-        else if (cap_at(p, tx, ty) != 1) ok = 0;
-        else {
-          int32_t occ = p.grid[((int64_t)tx * p.gy + ty) * p.cap];
-          if (occ >= 0 && p.macro_of[occ] != mid) ok = 0;
-        }
-      }
-      if (ok) atomicAdd(&m.counters[0], 1);
-    }
-    ok = __shfl(ok, 0);
-    if (!ok) return;
-    float dbb = 0.0f, dtd = 0.0f;
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64) {
-        int32_t n = p.blk_nets[k];
-        bool dup = false;
-        for (int32_t j2 = mm0; j2 < j && !dup; ++j2)
-          dup = blk_has_net(p, p.macro_blk[j2], n);
-        if (dup) continue;
-        dbb += net_bb_cost_macro(p, n, mid, ddx, ddy) - p.net_cost[n];
-        if (timing_tradeoff > 0.0f)
-          dtd += net_td_cost_macro(p, n, mid, ddx, ddy) - p.net_tcost[n];
-      }
-    }
-    dbb = wave_sum_f32(dbb);
-    dtd = wave_sum_f32(dtd);
-    float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
-                  timing_tradeoff * dtd * inv_td_norm;
-    bool accept;
-    if (delta <= 0.0f) accept = true;
-    else if (T <= 0.0f) accept = false;
-    else {
-      float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
-                (1.0f / 16777216.0f);
-      accept = u < __expf(-delta / T);
-    }
-    if (!accept) return;
-    if (lane == 0) {
-      atomicAdd(&m.counters[1], 1);
-      m.mv_blk[i] = blk;
-      m.mv_to[i] = ((ddx + 4096) << 13) | (ddy + 4096);
-      m.mv_other[i] = -2 - mid;
-      m.mv_dbb[i] = dbb;
-      m.mv_dtd[i] = dtd;
-      m.mv_flags[i] = 1;
-    }
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64)
-        atomicMin(&m.net_claim[p.blk_nets[k]], i);
-    }
-    for (int32_t j = mm0 + lane; j < mm1; j += 64) {
-      int32_t b = p.macro_blk[j];
-      atomicMin(&m.loc_claim[p.bx[b] * p.gy + p.by[b]], i);
-      atomicMin(&m.loc_claim[(p.bx[b] + ddx) * p.gy + p.by[b] + ddy], i);
-    }
-    return;
-  }
-  // -------- single-block move / swap (wave-uniform checks) --------
-  int32_t other = p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1];
-  if (other == blk) return;
-  if (other >= 0 && p.fixed && p.fixed[other]) return;
-  if (other >= 0 && p.macro_of && p.macro_of[other] >= 0)
-    return;   // never swap a chain member out from under its macro
-  if (lane == 0) atomicAdd(&m.counters[0], 1);  // valid proposals only
-  // exact deltas, lane-strided over the two blocks' net lists; nets
-  // shared by both blocks are counted once (skip in other's pass)
-  float dbb = 0.0f, dtd = 0.0f;
-  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64) {
-    int32_t n = p.blk_nets[k];
-    dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
-    if (timing_tradeoff > 0.0f)
-      dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
-  }
-  if (other >= 0) {
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64) {
-      int32_t n = p.blk_nets[k];
-      if (blk_has_net(p, blk, n)) continue;
-      dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
-      if (timing_tradeoff > 0.0f)
-        dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
-    }
-  }
-  dbb = wave_sum_f32(dbb);
-  dtd = wave_sum_f32(dtd);
-  float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
-                timing_tradeoff * dtd * inv_td_norm;
-  bool accept;
-  if (delta <= 0.0f) accept = true;
-  else if (T <= 0.0f) accept = false;
-  else {
-    float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
-              (1.0f / 16777216.0f);
-    accept = u < __expf(-delta / T);
-  }
-  if (!accept) return;
-  if (lane == 0) {
-    atomicAdd(&m.counters[1], 1);
-    m.mv_blk[i] = blk;
-    m.mv_to[i] = ((x1 * p.gy + y1) * p.cap + slot1);
-    m.mv_other[i] = other;
-    m.mv_dbb[i] = dbb;
-    m.mv_dtd[i] = dtd;
-    m.mv_flags[i] = 1;
-    atomicMin(&m.loc_claim[x0 * p.gy + y0], i);
-    atomicMin(&m.loc_claim[x1 * p.gy + y1], i);
-  }
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64)
-    atomicMin(&m.net_claim[p.blk_nets[k]], i);
-  if (other >= 0)
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64)
-      atomicMin(&m.net_claim[p.blk_nets[k]], i);
+// f(n) for each net n of block b, strided over the wave's lanes
+template <class F> __device__ __forceinline__
+void for_blk_nets(const PlaceDev& p, int32_t b, F f) {
+  for (int32_t k = p.blk_net_ptr[b] + (threadIdx.x & 63);
+       k < p.blk_net_ptr[b + 1]; k += 64)
+    f(p.blk_nets[k]);
+}
+// f(j, n) for each net n of each member macro_blk[j] of a macro
+template <class F> __device__ __forceinline__
+void for_macro_nets(const PlaceDev& p, int32_t mm0, int32_t mm1, F f) {
+  for (int32_t j = mm0; j < mm1; ++j)
+    for_blk_nets(p, p.macro_blk[j], [&](int32_t n) { f(j, n); });
 }
 
+// ---- claim policies ------------------------------------------------
+// A move takes the word of every net and tile it touches and wins if it
+// still holds them all after every move of the batch has taken its own.
+// Both policies give a word to the lowest move index that took it.
+// MinClaims (pnr_place_batch): int32 words, reset to INT_MAX before every
+// batch, taken with atomicMin of the move index.
+struct MinClaims {
+  int32_t* net; int32_t* loc; int32_t mine;
+  __device__ __forceinline__ void take_net(int n) const { atomicMin(&net[n], mine); }
+  __device__ __forceinline__ void take_loc(int t) const { atomicMin(&loc[t], mine); }
+  __device__ __forceinline__ bool holds_net(int n) const { return net[n] == mine; }
+  __device__ __forceinline__ bool holds_loc(int t) const { return loc[t] == mine; }
+};
+// EpochClaims (pnr_place_run): 64-bit epoch keys taken with atomicMax,
+//   key = (uint64(batch) << 32) | (0xFFFFFFFF - move index)
+// A later batch beats every stale word, so the arrays are zeroed once at
+// construction (batch numbers start at 1) and never reset; within a batch
+// the lowest move index has the largest key. The batch counter is 32
+// bits: it wraps after 4 G batches and nothing guards against that.
+struct EpochClaims {
+  unsigned long long* net; unsigned long long* loc; unsigned long long mine;
+  __device__ __forceinline__ void take_net(int n) const { atomicMax(&net[n], mine); }
+  __device__ __forceinline__ void take_loc(int t) const { atomicMax(&loc[t], mine); }
+  __device__ __forceinline__ bool holds_net(int n) const { return net[n] == mine; }
+  __device__ __forceinline__ bool holds_loc(int t) const { return loc[t] == mine; }
+};
+
+__device__ __forceinline__ unsigned long long claim_key(uint32_t batch, int i) {
+  return ((unsigned long long)batch << 32) | (0xFFFFFFFFu - (uint32_t)i);
+}
+
+// ---- propose -------------------------------------------------------
 // lane-0 candidate selection (same RNG stream as the round-1 per-thread
 // kernel); returns the block or -1, target via out-params
-__device__ int propose_select_impl(const PlaceDev& p, int rlim,
-                                   uint32_t seed, uint32_t batch, int i,
-                                   int& x1o, int& y1o, int& slot1o) {
+__device__ __forceinline__
+int propose_select(const PlaceDev& p, int rlim, uint32_t seed, uint32_t batch,
+                   int i, int& x1o, int& y1o, int& slot1o) {
   uint32_t r0 = rng_hash(seed ^ 0x5BD1E995u, batch, i);
   int32_t blk = r0 % p.num_blocks;
   if (p.fixed && p.fixed[blk]) return -1;
@@ -414,184 +286,83 @@ __device__ int propose_select_impl(const PlaceDev& p, int rlim,
   return blk;
 }
 
-__launch_bounds__(64 * PROP_WAVES, 2)
-__global__ void place_resolve_kernel(PlaceDev p, MovesDev m) {
+// may every member of macro ms.mid shift by (ddx, ddy)? (lane 0 only)
+__device__ __forceinline__
+bool macro_shift_ok(const PlaceDev& p, const MacroPos& ms, int32_t mm0,
+                    int32_t mm1) {
+  for (int32_t j = mm0; j < mm1; ++j) {
+    int32_t b = p.macro_blk[j];
+    int sx = p.bx[b], sy = p.by[b];
+    int tx = sx + ms.ddx, ty = sy + ms.ddy;
+    if (p.fixed && p.fixed[b]) return false;
+    if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) return false;
+    if (p.rx0 >= 0 && (tx < p.rx0 || tx > p.rx1 ||
+                       sx < p.rx0 || sx > p.rx1)) return false;
+    if (p.tile_btype
+            ? (p.tile_btype[tx * p.gy + ty] != p.blk_type[b])
+            : (is_io_loc(p, tx, ty) != (p.blk_type[b] == 0))) return false;
+    if (cap_at(p, tx, ty) != 1) return false;
+    int32_t occ = p.grid[((int64_t)tx * p.gy + ty) * p.cap];
+    if (occ >= 0 && p.macro_of[occ] != ms.mid) return false;
+  }
+  return true;
+}
+
+// this lane's share of net n's exact delta under `pos`
+template <class Pos> __device__ __forceinline__
+void add_net_delta(const PlaceDev& p, int32_t n, const Pos& pos,
+                   float timing_tradeoff, float& dbb, float& dtd) {
+  dbb += net_bb_cost(p, n, pos) - p.net_cost[n];
+  if (timing_tradeoff > 0.0f)
+    dtd += net_td_cost(p, n, pos) - p.net_tcost[n];
+}
+
+// Reduces the lanes' delta shares over the wave (dbb and dtd come back
+// summed) and takes the Metropolis decision, the same in every lane.
+__device__ __forceinline__
+bool metropolis(const Sched& s, int i, float& dbb, float& dtd) {
+  dbb = wave_sum_f32(dbb);
+  dtd = wave_sum_f32(dtd);
+  float delta = (1.0f - s.timing_tradeoff) * dbb * s.inv_bb_norm +
+                s.timing_tradeoff * dtd * s.inv_td_norm;
+  if (delta <= 0.0f) return true;
+  if (s.T <= 0.0f) return false;
+  float u = (rng_hash(s.seed, s.batch, i * 131 + 5) & 0xFFFFFF) *
+            (1.0f / 16777216.0f);
+  return u < __expf(-delta / s.T);
+}
+
+// lane 0 records an accepted move for resolve and apply. `from` is the
+// proposer's source tile: resolve must not read it from bx/by, which the
+// winners of a fused commit launch are rewriting.
+__device__ __forceinline__
+void record_move(const MovesDev& m, int32_t* mv_from, int i, int32_t blk,
+                 int32_t to, int32_t other, float dbb, float dtd,
+                 int32_t from) {
+  atomicAdd(&m.counters[1], 1);
+  m.mv_blk[i] = blk;
+  m.mv_to[i] = to;
+  m.mv_other[i] = other;
+  m.mv_dbb[i] = dbb;
+  m.mv_dtd[i] = dtd;
+  m.mv_flags[i] = 1;
+  mv_from[i] = from;
+}
+
+// One WAVEFRONT per proposal (the per-thread version left ~1 live
+// thread per CU and propose was 52% of LU32 kernel time at 158 us per
+// 554-move batch): lane 0 selects the candidate, the wave evaluates the
+// affected nets' exact deltas in parallel and reduces them, and claims
+// go out lane-strided (taking a claim is idempotent, so the block lists
+// need no dedup — only the delta sum skips shared nets).
+template <class Claims> __device__ __forceinline__
+void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
+                  int32_t* mv_from, int i, const Sched& s) {
   const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
-  if (i >= m.n_moves || m.mv_flags[i] != 1) return;
-  int32_t blk = m.mv_blk[i];
-  int32_t other = m.mv_other[i];
-  int32_t to = m.mv_to[i];
-  bool bad = false;
-  if (other <= -2) {
-    // macro move: every member's src+dst tile and every member net
-    const int mid = -2 - other;
-    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
-    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
-    for (int32_t j = mm0 + lane; j < mm1; j += 64) {
-      int32_t b = p.macro_blk[j];
-      int sx = p.bx[b], sy = p.by[b];
-      if (m.loc_claim[sx * p.gy + sy] != i ||
-          m.loc_claim[(sx + ddx) * p.gy + sy + ddy] != i) bad = true;
-    }
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64)
-        if (m.net_claim[p.blk_nets[k]] != i) bad = true;
-    }
-  } else {
-    int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
-    int x0 = p.bx[blk], y0 = p.by[blk];
-    if (lane == 0 && (m.loc_claim[x0 * p.gy + y0] != i ||
-                      m.loc_claim[x1 * p.gy + y1] != i)) bad = true;
-    for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-         k += 64)
-      if (m.net_claim[p.blk_nets[k]] != i) bad = true;
-    if (other >= 0)
-      for (int32_t k = p.blk_net_ptr[other] + lane;
-           k < p.blk_net_ptr[other + 1]; k += 64)
-        if (m.net_claim[p.blk_nets[k]] != i) bad = true;
-  }
-  const bool win = !__any(bad);
-  if (lane == 0) {
-    if (!win) { m.mv_flags[i] = 0; atomicAdd(&m.counters[3], 1); }
-    else { m.mv_flags[i] = 2; atomicAdd(&m.counters[2], 1); }
-  }
-}
-
-__launch_bounds__(64 * PROP_WAVES, 2)
-__global__ void place_apply_kernel(PlaceDev p, MovesDev m, float timing_tradeoff,
-                                   double* cost_acc /*[2]: dbb, dtd*/) {
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
-  if (i >= m.n_moves || m.mv_flags[i] != 2) return;
-  int32_t blk = m.mv_blk[i];
-  int32_t other = m.mv_other[i];
-  int32_t to = m.mv_to[i];
-  // Net-cost refresh runs FIRST, lane-strided, using the override cost
-  // functions on the PRE-move positions (so lanes never read positions
-  // another lane just wrote); duplicate refreshes of nets shared by both
-  // blocks are idempotent. Then lane 0 commits the grid/position update.
-  if (other <= -2) {
-    const int mid = -2 - other;
-    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
-    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64) {
-        int32_t n = p.blk_nets[k];
-        p.net_cost[n] = net_bb_cost_macro(p, n, mid, ddx, ddy);
-        if (timing_tradeoff > 0.0f)
-          p.net_tcost[n] = net_td_cost_macro(p, n, mid, ddx, ddy);
-      }
-    }
-    if (lane == 0) {
-      for (int32_t j = mm0; j < mm1; ++j) {
-        int32_t b = p.macro_blk[j];
-        p.grid[((int64_t)p.bx[b] * p.gy + p.by[b]) * p.cap + p.bslot[b]] = -1;
-      }
-      for (int32_t j = mm0; j < mm1; ++j) {
-        int32_t b = p.macro_blk[j];
-        int tx = p.bx[b] + ddx, ty = p.by[b] + ddy;
-        p.grid[((int64_t)tx * p.gy + ty) * p.cap] = b;
-        p.bx[b] = tx; p.by[b] = ty; p.bslot[b] = 0;
-      }
-      unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
-      unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
-    }
-    return;
-  }
-  int slot1 = to % p.cap;
-  int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
-  int x0 = p.bx[blk], y0 = p.by[blk], s0 = p.bslot[blk];
-  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64) {
-    int32_t n = p.blk_nets[k];
-    p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
-    if (timing_tradeoff > 0.0f)
-      p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
-  }
-  if (other >= 0)
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64) {
-      int32_t n = p.blk_nets[k];
-      p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
-      if (timing_tradeoff > 0.0f)
-        p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
-    }
-  if (lane == 0) {
-    p.grid[((int64_t)x0 * p.gy + y0) * p.cap + s0] = other >= 0 ? other : -1;
-    p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1] = blk;
-    p.bx[blk] = x1; p.by[blk] = y1; p.bslot[blk] = slot1;
-    if (other >= 0) { p.bx[other] = x0; p.by[other] = y0; p.bslot[other] = s0; }
-    unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
-    unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
-  }
-}
-
-// claims reset per batch; counters accumulate across batches (host zeroes
-// them per run_batches call) so the schedule sees the TRUE accept rate.
-__global__ void place_reset_claims_kernel(int32_t* net_claim, int32_t nn,
-                                          int32_t* loc_claim, int32_t nl,
-                                          int32_t* counters) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  int total = max(nn, nl);
-  (void)counters;
-  for (; i < total; i += gridDim.x * blockDim.x) {
-    if (i < nn) net_claim[i] = 0x7FFFFFFF;
-    if (i < nl) loc_claim[i] = 0x7FFFFFFF;
-  }
-}
-
-// ===================================================================
-// Native run loop (pnr_place_run): two launches per batch, no reset, no
-// host round trip per batch. The four kernels above stay as they are
-// and serve as the oracle (GpuPlacer(legacy_batches=True)).
-//
-// Claims are 64-bit epoch keys taken with atomicMax:
-//   key = (uint64(batch) << 32) | (0xFFFFFFFF - move index)
-// A later batch beats every stale word, so the claim arrays are zeroed
-// once at construction (batch numbers start at 1) and never reset; within
-// a batch the lowest move index has the largest key, so the winner set is
-// the one atomicMin on the move index gives. "I hold this claim" is
-// claim == my key. The batch counter is 32 bits: it wraps after 4 G
-// batches and nothing guards against that.
-//
-// Control block ctrl[4] (device, zeroed by the host per run_batches call):
-//   [0] done     set by the stop rule; every kernel returns at once on it
-//   [1] n_exec   batches executed so far in this run_batches call
-//   [2] ticket   workgroup arrival counter of a checking commit launch
-struct RunDev {
-  int32_t* mv_from;                  // proposer's source tile x*gy+y
-  unsigned long long* net_claim;     // [num_nets] epoch keys
-  unsigned long long* loc_claim;     // [gx*gy] epoch keys
-  int32_t* ctrl;
-};
-
-__device__ __forceinline__ unsigned long long claim_key(uint32_t batch, int i) {
-  return ((unsigned long long)batch << 32) | (0xFFFFFFFFu - (uint32_t)i);
-}
-
-// place_propose_kernel with epoch-key claims, the done word and mv_from;
-// selection, deltas and Metropolis are the same code in the same order.
-__launch_bounds__(64 * PROP_WAVES, 2)
-__global__ void place_propose_run_kernel(PlaceDev p, MovesDev m, RunDev r,
-                                         float T, int rlim,
-                                         float timing_tradeoff,
-                                         float inv_bb_norm, float inv_td_norm,
-                                         uint32_t seed, uint32_t batch) {
-  if (r.ctrl[0]) return;
-  const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
-  if (i >= m.n_moves) return;
-  const unsigned long long key = claim_key(batch, i);
   int sel = -1, sx1 = -1, sy1 = -1, sslot = 0;
   if (lane == 0) {
     m.mv_flags[i] = 0;
-    sel = propose_select_impl(p, rlim, seed, batch, i, sx1, sy1, sslot);
+    sel = propose_select(p, s.rlim, s.seed, s.batch, i, sx1, sy1, sslot);
   }
   sel = __shfl(sel, 0);
   if (sel < 0) return;
@@ -601,218 +372,146 @@ __global__ void place_propose_run_kernel(PlaceDev p, MovesDev m, RunDev r,
   const int32_t blk = sel;
   const int x0 = p.bx[blk], y0 = p.by[blk];
   const int mid = p.macro_of ? p.macro_of[blk] : -1;
+  float dbb = 0.0f, dtd = 0.0f;
   if (mid >= 0) {
-    const int ddx = x1 - x0, ddy = y1 - y0;
+    // -------- macro move (reference: place_macro.c; free-target) -----
+    const MacroPos ms{mid, x1 - x0, y1 - y0};
     const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
     if (mm1 - mm0 > 16) return;
     int ok = 0;
     if (lane == 0) {
-      ok = 1;
-      for (int32_t j = mm0; j < mm1 && ok; ++j) {
-        int32_t b = p.macro_blk[j];
-        int sx = p.bx[b], sy = p.by[b];
-        int tx = sx + ddx, ty = sy + ddy;
-        if (p.fixed && p.fixed[b]) ok = 0;
-        else if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) ok = 0;
-        else if (p.rx0 >= 0 && (tx < p.rx0 || tx > p.rx1 ||
-                                sx < p.rx0 || sx > p.rx1)) ok = 0;
-        else if (p.tile_btype
-                     ? (p.tile_btype[tx * p.gy + ty] != p.blk_type[b])
-                     : (is_io_loc(p, tx, ty) != (p.blk_type[b] == 0))) ok = 0;
-        else if (cap_at(p, tx, ty) != 1) ok = 0;
-        else {
-          int32_t occ = p.grid[((int64_t)tx * p.gy + ty) * p.cap];
-          if (occ >= 0 && p.macro_of[occ] != mid) ok = 0;
-        }
-      }
+      ok = macro_shift_ok(p, ms, mm0, mm1);
       if (ok) atomicAdd(&m.counters[0], 1);
     }
     ok = __shfl(ok, 0);
     if (!ok) return;
-    float dbb = 0.0f, dtd = 0.0f;
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64) {
-        int32_t n = p.blk_nets[k];
-        bool dup = false;
-        for (int32_t j2 = mm0; j2 < j && !dup; ++j2)
-          dup = blk_has_net(p, p.macro_blk[j2], n);
-        if (dup) continue;
-        dbb += net_bb_cost_macro(p, n, mid, ddx, ddy) - p.net_cost[n];
-        if (timing_tradeoff > 0.0f)
-          dtd += net_td_cost_macro(p, n, mid, ddx, ddy) - p.net_tcost[n];
-      }
-    }
-    dbb = wave_sum_f32(dbb);
-    dtd = wave_sum_f32(dtd);
-    float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
-                  timing_tradeoff * dtd * inv_td_norm;
-    bool accept;
-    if (delta <= 0.0f) accept = true;
-    else if (T <= 0.0f) accept = false;
-    else {
-      float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
-                (1.0f / 16777216.0f);
-      accept = u < __expf(-delta / T);
-    }
-    if (!accept) return;
-    if (lane == 0) {
-      atomicAdd(&m.counters[1], 1);
-      m.mv_blk[i] = blk;
-      m.mv_to[i] = ((ddx + 4096) << 13) | (ddy + 4096);
-      m.mv_other[i] = -2 - mid;
-      m.mv_dbb[i] = dbb;
-      m.mv_dtd[i] = dtd;
-      m.mv_flags[i] = 1;
-      r.mv_from[i] = x0 * p.gy + y0;
-    }
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64)
-        atomicMax(&r.net_claim[p.blk_nets[k]], key);
-    }
+    // a net of several members is counted at the first of them
+    for_macro_nets(p, mm0, mm1, [&](int32_t j, int32_t n) {
+      bool dup = false;
+      for (int32_t j2 = mm0; j2 < j && !dup; ++j2)
+        dup = blk_has_net(p, p.macro_blk[j2], n);
+      if (!dup) add_net_delta(p, n, ms, s.timing_tradeoff, dbb, dtd);
+    });
+    if (!metropolis(s, i, dbb, dtd)) return;
+    if (lane == 0)
+      record_move(m, mv_from, i, blk,
+                  ((ms.ddx + 4096) << 13) | (ms.ddy + 4096), -2 - mid, dbb,
+                  dtd, x0 * p.gy + y0);
+    for_macro_nets(p, mm0, mm1, [&](int32_t, int32_t n) { c.take_net(n); });
     for (int32_t j = mm0 + lane; j < mm1; j += 64) {
       int32_t b = p.macro_blk[j];
-      atomicMax(&r.loc_claim[p.bx[b] * p.gy + p.by[b]], key);
-      atomicMax(&r.loc_claim[(p.bx[b] + ddx) * p.gy + p.by[b] + ddy], key);
+      c.take_loc(p.bx[b] * p.gy + p.by[b]);
+      c.take_loc((p.bx[b] + ms.ddx) * p.gy + p.by[b] + ms.ddy);
     }
     return;
   }
+  // -------- single-block move / swap (wave-uniform checks) --------
   int32_t other = p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1];
   if (other == blk) return;
   if (other >= 0 && p.fixed && p.fixed[other]) return;
   if (other >= 0 && p.macro_of && p.macro_of[other] >= 0)
     return;   // never swap a chain member out from under its macro
   if (lane == 0) atomicAdd(&m.counters[0], 1);  // valid proposals only
-  float dbb = 0.0f, dtd = 0.0f;
-  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64) {
-    int32_t n = p.blk_nets[k];
-    dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
-    if (timing_tradeoff > 0.0f)
-      dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
-  }
-  if (other >= 0) {
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64) {
-      int32_t n = p.blk_nets[k];
-      if (blk_has_net(p, blk, n)) continue;
-      dbb += net_bb_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_cost[n];
-      if (timing_tradeoff > 0.0f)
-        dtd += net_td_cost(p, n, blk, x1, y1, other, ox, oy) - p.net_tcost[n];
-    }
-  }
-  dbb = wave_sum_f32(dbb);
-  dtd = wave_sum_f32(dtd);
-  float delta = (1.0f - timing_tradeoff) * dbb * inv_bb_norm +
-                timing_tradeoff * dtd * inv_td_norm;
-  bool accept;
-  if (delta <= 0.0f) accept = true;
-  else if (T <= 0.0f) accept = false;
-  else {
-    float u = (rng_hash(seed, batch, i * 131 + 5) & 0xFFFFFF) *
-              (1.0f / 16777216.0f);
-    accept = u < __expf(-delta / T);
-  }
-  if (!accept) return;
-  if (lane == 0) {
-    atomicAdd(&m.counters[1], 1);
-    m.mv_blk[i] = blk;
-    m.mv_to[i] = ((x1 * p.gy + y1) * p.cap + slot1);
-    m.mv_other[i] = other;
-    m.mv_dbb[i] = dbb;
-    m.mv_dtd[i] = dtd;
-    m.mv_flags[i] = 1;
-    r.mv_from[i] = x0 * p.gy + y0;
-    atomicMax(&r.loc_claim[x0 * p.gy + y0], key);
-    atomicMax(&r.loc_claim[x1 * p.gy + y1], key);
-  }
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64)
-    atomicMax(&r.net_claim[p.blk_nets[k]], key);
+  // nets shared by both blocks are counted once (skipped in other's pass)
+  const SwapPos sw{blk, x1, y1, other, other >= 0 ? x0 : -1000,
+                   other >= 0 ? y0 : -1000};
+  for_blk_nets(p, blk, [&](int32_t n) {
+    add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
+  });
   if (other >= 0)
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64)
-      atomicMax(&r.net_claim[p.blk_nets[k]], key);
+    for_blk_nets(p, other, [&](int32_t n) {
+      if (!blk_has_net(p, blk, n))
+        add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
+    });
+  if (!metropolis(s, i, dbb, dtd)) return;
+  if (lane == 0) {
+    record_move(m, mv_from, i, blk, (x1 * p.gy + y1) * p.cap + slot1, other,
+                dbb, dtd, x0 * p.gy + y0);
+    c.take_loc(x0 * p.gy + y0);
+    c.take_loc(x1 * p.gy + y1);
+  }
+  auto take = [&](int32_t n) { c.take_net(n); };
+  for_blk_nets(p, blk, take);
+  if (other >= 0) for_blk_nets(p, other, take);
 }
 
-// Resolve and apply of one move by its wave: the verdict of
-// place_resolve_kernel, then at once the body of place_apply_kernel for a
-// winner. Why no wave depends on what another writes in the same launch is
-// argued in docs/KERNELS.md (placer section); in short, the verdict of a
-// single move reads only claims and its own mv_* words (source tile from
-// mv_from, not bx/by), a winner's apply reads positions of blocks on nets
-// and tiles that it alone holds, and a macro proposal that can read a
-// position torn by the winning proposal of the same chain holds none of
-// that chain's source tiles and loses whatever it reads.
-__device__ void commit_move(const PlaceDev& p, const MovesDev& m,
-                            const RunDev& r, float timing_tradeoff,
-                            double* cost_acc, uint32_t batch) {
+// ---- resolve and apply, of a move as propose recorded it ------------
+struct Move {
+  int32_t blk, other, to;
+  __device__ __forceinline__ Move(const MovesDev& m, int i)
+      : blk(m.mv_blk[i]), other(m.mv_other[i]), to(m.mv_to[i]) {}
+  __device__ __forceinline__ bool is_macro() const { return other <= -2; }
+  __device__ __forceinline__ MacroPos macro() const {
+    return MacroPos{-2 - other, (to >> 13) - 4096, (to & 0x1FFF) - 4096};
+  }
+};
+
+// Verdict of accepted move i: does it hold every claim it took? Written
+// for the fused commit launch, where winners rewrite bx/by while other
+// waves still decide (why no verdict depends on that: docs/KERNELS.md,
+// placer section). So a single move's source tile comes from mv_from, and
+// a macro move, which must read its members' bx/by, tests the derived
+// tiles against the grid before loading their claims: a read torn by the
+// winning proposal of the same chain may point off it (such a wave has
+// lost already). In a resolve launch of its own bx/by are pre-batch:
+// mv_from equals what they give and the bounds test never fires.
+template <class Claims> __device__ __forceinline__
+bool resolve_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
+                  const int32_t* mv_from, int i, const Move& mv) {
   const int lane = threadIdx.x & 63;
-  const int i = blockIdx.x * PROP_WAVES + (threadIdx.x >> 6);
-  if (i >= m.n_moves || m.mv_flags[i] != 1) return;
-  const unsigned long long key = claim_key(batch, i);
-  int32_t blk = m.mv_blk[i];
-  int32_t other = m.mv_other[i];
-  int32_t to = m.mv_to[i];
   bool bad = false;
-  if (other <= -2) {
-    const int mid = -2 - other;
-    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
-    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
+  if (mv.is_macro()) {
+    // every member's src+dst tile and every member net
+    const MacroPos ms = mv.macro();
+    const int32_t mm0 = p.macro_ptr[ms.mid], mm1 = p.macro_ptr[ms.mid + 1];
     for (int32_t j = mm0 + lane; j < mm1; j += 64) {
       int32_t b = p.macro_blk[j];
       int sx = p.bx[b], sy = p.by[b];
-      int tx = sx + ddx, ty = sy + ddy;
-      // a torn read (see above) may point off the grid; such a wave has
-      // lost already, the test only keeps the claim load in bounds
+      int tx = sx + ms.ddx, ty = sy + ms.ddy;
       if (tx < 0 || tx >= p.gx || ty < 0 || ty >= p.gy) bad = true;
-      else if (r.loc_claim[sx * p.gy + sy] != key ||
-               r.loc_claim[tx * p.gy + ty] != key) bad = true;
+      else if (!c.holds_loc(sx * p.gy + sy) ||
+               !c.holds_loc(tx * p.gy + ty)) bad = true;
     }
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64)
-        if (r.net_claim[p.blk_nets[k]] != key) bad = true;
-    }
+    for_macro_nets(p, mm0, mm1, [&](int32_t, int32_t n) {
+      if (!c.holds_net(n)) bad = true;
+    });
   } else {
-    int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
-    if (lane == 0 && (r.loc_claim[r.mv_from[i]] != key ||
-                      r.loc_claim[x1 * p.gy + y1] != key)) bad = true;
-    for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-         k += 64)
-      if (r.net_claim[p.blk_nets[k]] != key) bad = true;
-    if (other >= 0)
-      for (int32_t k = p.blk_net_ptr[other] + lane;
-           k < p.blk_net_ptr[other + 1]; k += 64)
-        if (r.net_claim[p.blk_nets[k]] != key) bad = true;
+    int x1 = mv.to / p.cap / p.gy, y1 = (mv.to / p.cap) % p.gy;
+    if (lane == 0 && (!c.holds_loc(mv_from[i]) ||
+                      !c.holds_loc(x1 * p.gy + y1))) bad = true;
+    auto lost = [&](int32_t n) { if (!c.holds_net(n)) bad = true; };
+    for_blk_nets(p, mv.blk, lost);
+    if (mv.other >= 0) for_blk_nets(p, mv.other, lost);
   }
   const bool win = !__any(bad);
   if (lane == 0) {
     if (!win) { m.mv_flags[i] = 0; atomicAdd(&m.counters[3], 1); }
     else { m.mv_flags[i] = 2; atomicAdd(&m.counters[2], 1); }
   }
-  if (!win) return;
-  // ---- apply (net costs first on the pre-move positions, then lane 0
-  // commits grid and positions; same order as place_apply_kernel) ----
-  if (other <= -2) {
-    const int mid = -2 - other;
-    const int ddx = (to >> 13) - 4096, ddy = (to & 0x1FFF) - 4096;
-    const int32_t mm0 = p.macro_ptr[mid], mm1 = p.macro_ptr[mid + 1];
-    for (int32_t j = mm0; j < mm1; ++j) {
-      int32_t b = p.macro_blk[j];
-      for (int32_t k = p.blk_net_ptr[b] + lane; k < p.blk_net_ptr[b + 1];
-           k += 64) {
-        int32_t n = p.blk_nets[k];
-        p.net_cost[n] = net_bb_cost_macro(p, n, mid, ddx, ddy);
-        if (timing_tradeoff > 0.0f)
-          p.net_tcost[n] = net_td_cost_macro(p, n, mid, ddx, ddy);
-      }
-    }
+  return win;
+}
+
+template <class Pos> __device__ __forceinline__
+void refresh_net(const PlaceDev& p, int32_t n, const Pos& pos,
+                 float timing_tradeoff) {
+  p.net_cost[n] = net_bb_cost(p, n, pos);
+  if (timing_tradeoff > 0.0f) p.net_tcost[n] = net_td_cost(p, n, pos);
+}
+
+// Apply winner i. The net-cost refresh runs FIRST, lane-strided, with the
+// hypothetical positions over the PRE-move state (so lanes never read
+// positions another lane just wrote); duplicate refreshes of nets shared
+// by both blocks are idempotent. Then lane 0 commits grid and positions.
+__device__ __forceinline__
+void apply_move(const PlaceDev& p, const MovesDev& m, int i, const Move& mv,
+                float timing_tradeoff, double* cost_acc /*[2]: dbb, dtd*/) {
+  const int lane = threadIdx.x & 63;
+  if (mv.is_macro()) {
+    const MacroPos ms = mv.macro();
+    const int32_t mm0 = p.macro_ptr[ms.mid], mm1 = p.macro_ptr[ms.mid + 1];
+    for_macro_nets(p, mm0, mm1, [&](int32_t, int32_t n) {
+      refresh_net(p, n, ms, timing_tradeoff);
+    });
     if (lane == 0) {
       for (int32_t j = mm0; j < mm1; ++j) {
         int32_t b = p.macro_blk[j];
@@ -820,42 +519,105 @@ __device__ void commit_move(const PlaceDev& p, const MovesDev& m,
       }
       for (int32_t j = mm0; j < mm1; ++j) {
         int32_t b = p.macro_blk[j];
-        int tx = p.bx[b] + ddx, ty = p.by[b] + ddy;
+        int tx = p.bx[b] + ms.ddx, ty = p.by[b] + ms.ddy;
         p.grid[((int64_t)tx * p.gy + ty) * p.cap] = b;
         p.bx[b] = tx; p.by[b] = ty; p.bslot[b] = 0;
       }
-      unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
-      unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
     }
-    return;
-  }
-  int slot1 = to % p.cap;
-  int x1 = to / p.cap / p.gy, y1 = (to / p.cap) % p.gy;
-  int x0 = p.bx[blk], y0 = p.by[blk], s0 = p.bslot[blk];
-  const int ox = other >= 0 ? x0 : -1000, oy = other >= 0 ? y0 : -1000;
-  for (int32_t k = p.blk_net_ptr[blk] + lane; k < p.blk_net_ptr[blk + 1];
-       k += 64) {
-    int32_t n = p.blk_nets[k];
-    p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
-    if (timing_tradeoff > 0.0f)
-      p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
-  }
-  if (other >= 0)
-    for (int32_t k = p.blk_net_ptr[other] + lane;
-         k < p.blk_net_ptr[other + 1]; k += 64) {
-      int32_t n = p.blk_nets[k];
-      p.net_cost[n] = net_bb_cost(p, n, blk, x1, y1, other, ox, oy);
-      if (timing_tradeoff > 0.0f)
-        p.net_tcost[n] = net_td_cost(p, n, blk, x1, y1, other, ox, oy);
+  } else {
+    const int32_t blk = mv.blk, other = mv.other;
+    int slot1 = mv.to % p.cap;
+    int x1 = mv.to / p.cap / p.gy, y1 = (mv.to / p.cap) % p.gy;
+    int x0 = p.bx[blk], y0 = p.by[blk], s0 = p.bslot[blk];
+    const SwapPos sw{blk, x1, y1, other, other >= 0 ? x0 : -1000,
+                     other >= 0 ? y0 : -1000};
+    auto refresh = [&](int32_t n) { refresh_net(p, n, sw, timing_tradeoff); };
+    for_blk_nets(p, blk, refresh);
+    if (other >= 0) for_blk_nets(p, other, refresh);
+    if (lane == 0) {
+      p.grid[((int64_t)x0 * p.gy + y0) * p.cap + s0] = other >= 0 ? other : -1;
+      p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1] = blk;
+      p.bx[blk] = x1; p.by[blk] = y1; p.bslot[blk] = slot1;
+      if (other >= 0) { p.bx[other] = x0; p.by[other] = y0; p.bslot[other] = s0; }
     }
+  }
   if (lane == 0) {
-    p.grid[((int64_t)x0 * p.gy + y0) * p.cap + s0] = other >= 0 ? other : -1;
-    p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1] = blk;
-    p.bx[blk] = x1; p.by[blk] = y1; p.bslot[blk] = slot1;
-    if (other >= 0) { p.bx[other] = x0; p.by[other] = y0; p.bslot[other] = s0; }
     unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
     unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
   }
+}
+
+// ---- pnr_place_batch: reset, propose, resolve, apply ---------------
+// MinClaims words back to INT_MAX, before every batch
+__global__ void place_reset_claims_kernel(int32_t* net_claim, int32_t nn,
+                                          int32_t* loc_claim, int32_t nl) {
+  int i = blockIdx.x * blockDim.x + threadIdx.x;
+  int total = max(nn, nl);
+  for (; i < total; i += gridDim.x * blockDim.x) {
+    if (i < nn) net_claim[i] = 0x7FFFFFFF;
+    if (i < nl) loc_claim[i] = 0x7FFFFFFF;
+  }
+}
+
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_propose_kernel(PlaceDev p, MovesDev m, int32_t* mv_from,
+                                     Sched s) {
+  const int i = move_index();
+  if (i >= m.n_moves) return;
+  propose_move(p, m, MinClaims{m.net_claim, m.loc_claim, i}, mv_from, i, s);
+}
+
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_resolve_kernel(PlaceDev p, MovesDev m,
+                                     const int32_t* mv_from) {
+  const int i = move_index();
+  if (i >= m.n_moves || m.mv_flags[i] != 1) return;
+  resolve_move(p, m, MinClaims{m.net_claim, m.loc_claim, i}, mv_from, i,
+               Move(m, i));
+}
+
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_apply_kernel(PlaceDev p, MovesDev m,
+                                   float timing_tradeoff, double* cost_acc) {
+  const int i = move_index();
+  if (i >= m.n_moves || m.mv_flags[i] != 2) return;
+  apply_move(p, m, i, Move(m, i), timing_tradeoff, cost_acc);
+}
+
+// ---- pnr_place_run: propose, commit --------------------------------
+// Two launches per batch, no reset, no host round trip per batch.
+// Control block ctrl[4] (device, zeroed by the host per run_batches call):
+//   [0] done     set by the stop rule; every kernel returns at once on it
+//   [1] n_exec   batches executed so far in this run_batches call
+//   [2] ticket   workgroup arrival counter of a checking commit launch
+struct RunDev {
+  int32_t* mv_from;                  // proposer's source tile x*gy+y
+  unsigned long long* net_claim;     // [num_nets] EpochClaims words
+  unsigned long long* loc_claim;     // [gx*gy]
+  int32_t* ctrl;
+};
+
+__launch_bounds__(64 * PROP_WAVES, 2)
+__global__ void place_propose_run_kernel(PlaceDev p, MovesDev m, RunDev r,
+                                         Sched s) {
+  if (r.ctrl[0]) return;
+  const int i = move_index();
+  if (i >= m.n_moves) return;
+  const EpochClaims c{r.net_claim, r.loc_claim, claim_key(s.batch, i)};
+  propose_move(p, m, c, r.mv_from, i, s);
+}
+
+// Resolve and apply of one move by its wave: a winner applies at once,
+// while other waves are still deciding (see resolve_move).
+__device__ __forceinline__
+void commit_move(const PlaceDev& p, const MovesDev& m, const RunDev& r,
+                 float timing_tradeoff, double* cost_acc, uint32_t batch) {
+  const int i = move_index();
+  if (i >= m.n_moves || m.mv_flags[i] != 1) return;
+  const Move mv(m, i);
+  const EpochClaims c{r.net_claim, r.loc_claim, claim_key(batch, i)};
+  if (resolve_move(p, m, c, r.mv_from, i, mv))
+    apply_move(p, m, i, mv, timing_tradeoff, cost_acc);
 }
 
 // check != 0 on the 4th, 8th, ... batch of a run_batches call: the last
@@ -898,11 +660,11 @@ __global__ void place_refresh_costs_kernel(PlaceDev p, float timing_tradeoff,
                                            double* out /*[2]*/) {
   int n = blockIdx.x * blockDim.x + threadIdx.x;
   for (; n < p.num_nets; n += gridDim.x * blockDim.x) {
-    float c = net_bb_cost(p, n, -1, 0, 0, -1, 0, 0);
+    const SwapPos as_is{-1, 0, 0, -1, 0, 0};
+    float c = net_bb_cost(p, n, as_is);
     p.net_cost[n] = c;
     unsafeAtomicAdd(&out[0], (double)c);
-    float t = (timing_tradeoff > 0.0f)
-                  ? net_td_cost(p, n, -1, 0, 0, -1, 0, 0) : 0.0f;
+    float t = timing_tradeoff > 0.0f ? net_td_cost(p, n, as_is) : 0.0f;
     p.net_tcost[n] = t;
     unsafeAtomicAdd(&out[1], (double)t);
   }
@@ -968,22 +730,26 @@ static void unpack(const PlaceLaunchArgs* a, PlaceDev& p, MovesDev& m) {
   m.counters = a->counters; m.n_moves = a->n_moves;
 }
 
+static Sched sched(const PlaceLaunchArgs* a, uint32_t batch) {
+  return Sched{a->T, a->rlim, a->timing_tradeoff, a->inv_bb_norm,
+               a->inv_td_norm, a->seed, batch};
+}
+
 int pnr_place_batch(const PlaceLaunchArgs* a, void* stream) {
+  if (!a->mv_from || !a->net_claim || !a->loc_claim)
+    return (int)hipErrorInvalidValue;
   PlaceDev p; MovesDev m;
   unpack(a, p, m);
   hipStream_t s = (hipStream_t)stream;
   int rg = (max(max(a->num_nets, a->gx * a->gy), a->n_moves) + 255) / 256;
   rg = rg < 2048 ? rg : 2048;
   hipLaunchKernelGGL(place_reset_claims_kernel, dim3(rg), dim3(256), 0, s,
-                     m.net_claim, p.num_nets, m.loc_claim, p.gx * p.gy,
-                     m.counters);
-  // one wave64 per proposal, PROP_WAVES waves per workgroup
+                     m.net_claim, p.num_nets, m.loc_claim, p.gx * p.gy);
   int mg = (m.n_moves + PROP_WAVES - 1) / PROP_WAVES;
   hipLaunchKernelGGL(place_propose_kernel, dim3(mg), dim3(64 * PROP_WAVES),
-                     0, s, p, m, a->T, a->rlim, a->timing_tradeoff,
-                     a->inv_bb_norm, a->inv_td_norm, a->seed, a->batch);
+                     0, s, p, m, a->mv_from, sched(a, a->batch));
   hipLaunchKernelGGL(place_resolve_kernel, dim3(mg), dim3(64 * PROP_WAVES),
-                     0, s, p, m);
+                     0, s, p, m, (const int32_t*)a->mv_from);
   hipLaunchKernelGGL(place_apply_kernel, dim3(mg), dim3(64 * PROP_WAVES),
                      0, s, p, m, a->timing_tradeoff, a->cost_acc);
   return (int)hipGetLastError();
@@ -1011,9 +777,7 @@ int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
   for (int32_t k = 0; k < n_batches; ++k) {
     const uint32_t batch = first_batch + (uint32_t)k;
     hipLaunchKernelGGL(place_propose_run_kernel, dim3(mg),
-                       dim3(64 * PROP_WAVES), 0, s, p, m, r, a->T, a->rlim,
-                       a->timing_tradeoff, a->inv_bb_norm, a->inv_td_norm,
-                       a->seed, batch);
+                       dim3(64 * PROP_WAVES), 0, s, p, m, r, sched(a, batch));
     hipLaunchKernelGGL(place_commit_kernel, dim3(mg), dim3(64 * PROP_WAVES),
                        0, s, p, m, r, a->timing_tradeoff, a->cost_acc, batch,
                        (int)(((k + 1) & 3) == 0), target_moves);
@@ -1025,7 +789,7 @@ int pnr_place_refresh(const PlaceLaunchArgs* a, void* stream) {
   PlaceDev p; MovesDev m;
   unpack(a, p, m);
   hipStream_t s = (hipStream_t)stream;
-  // single-block prologue zeroes out; then grid-stride accumulate
+  // the caller has zeroed cost_acc; grid-stride accumulate
   hipLaunchKernelGGL(place_refresh_costs_kernel, dim3(1024), dim3(256), 0, s,
                      p, a->timing_tradeoff, a->cost_acc);
   return (int)hipGetLastError();

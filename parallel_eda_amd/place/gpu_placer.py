@@ -7,7 +7,10 @@ exclusive net+tile claims are sequential-equivalent (disjoint winners,
 exact deltas), so the anneal semantics match the reference's try_swap loop
 at a per-batch granularity. The earlier driver, one four-kernel
 pnr_place_batch call per batch, stays selectable (legacy_batches=True) as
-the oracle the run loop is tested against.
+the oracle the run loop is tested against. Both drivers run the same
+device code for propose, resolve and apply; they differ in how claims are
+taken (reset + atomicMin, or epoch keys), in the launches per batch and
+in where the stop rule runs.
 """
 import ctypes as ct
 import math

@@ -5,8 +5,17 @@ epoch-key claims, device-side stop rule) against the legacy batch loop
 The two paths must agree bit for bit, so every comparison here is exact.
 Each scenario is driven once per path and the recorded states are shared
 by the tests; a second legacy drive is the control that shows the oracle
-itself is reproducible."""
+itself is reproducible.
+
+Both drivers share one propose/resolve/apply body, so their agreement no
+longer shows that the body computes what it did before it was shared.
+tests/golden/place_run_digests.json pins that: digests of every snapshot
+recorded from the last commit with two separate bodies
+(tools/record_place_digests.py)."""
 import functools
+import hashlib
+import json
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -17,10 +26,12 @@ from parallel_eda_amd.timing.sta import STA
 
 pytestmark = pytest.mark.gpu
 
-CASES = ["tseng", "tiny_het", "tseng_macros"]
+CASES = ["tseng", "tiny_het", "tseng_macros", "tseng_fixed"]
 STATE = ["t_bx", "t_by", "t_bslot", "t_grid", "t_net_cost", "t_net_tcost",
          "t_mv_flags", "t_mv_dbb", "t_mv_dtd"]
 BIG = 10 ** 9       # a target_moves no run reaches: the run goes to its cap
+N_PINNED = 8        # tseng_fixed: the lowest-numbered IO blocks are pinned
+DIGESTS = Path(__file__).parent / "golden" / "place_run_digests.json"
 
 
 @functools.lru_cache(maxsize=None)
@@ -31,7 +42,7 @@ def _case(name):
         return arch, nl, 1, None
     arch = get_arch("tseng")
     nl = synth_netlist(spec_for_arch(arch, fill=0.5, seed=4))
-    if name == "tseng":
+    if name in ("tseng", "tseng_fixed"):
         return arch, nl, 4, None
     # the two carry chains of test_gpu_place.py::test_gpu_macro_moves
     clbs = np.nonzero(np.asarray(nl.block_type) == 1)[0]
@@ -40,6 +51,22 @@ def _case(name):
               [(int(clbs[3]), 0, 0), (int(clbs[4]), 0, 1),
                (int(clbs[5]), 0, 2), (int(clbs[6]), 0, 3)]]
     return arch, nl, 11, macros
+
+
+@functools.lru_cache(maxsize=None)
+def _pins(name):
+    """fixed=(ids, x, y, slot) of a scenario, or None. tseng_fixed pins
+    blocks where an unpinned placer of the same seed puts them at first,
+    so the pin-down teleport is a no-op and the placement stays legal."""
+    if name != "tseng_fixed":
+        return None
+    from parallel_eda_amd.place.gpu_placer import GpuPlacer
+    arch, nl, seed, _ = _case(name)
+    ids = np.nonzero(np.asarray(nl.block_type) == 0)[0][:N_PINNED]
+    assert len(ids) == N_PINNED
+    free = GpuPlacer(nl, arch, seed=seed)
+    return (ids,) + tuple(t.cpu().numpy()[ids]
+                          for t in (free.t_bx, free.t_by, free.t_bslot))
 
 
 def _snapshot(p, ret):
@@ -58,7 +85,7 @@ def _drive(name, timing, legacy, instance=0):
     from parallel_eda_amd.place.gpu_placer import GpuPlacer
     arch, nl, seed, macros = _case(name)
     p = GpuPlacer(nl, arch, seed=seed, timing=timing, macros=macros,
-                  legacy_batches=legacy)
+                  fixed=_pins(name), legacy_batches=legacy)
     tt = 0.0
     if timing:
         # criticalities from the initial placement, as the anneal does
@@ -136,6 +163,60 @@ def test_legacy_loop_is_reproducible(name, timing):
 def test_run_loop_matches_legacy(name, timing):
     _assert_same(_drive(name, timing, False), _drive(name, timing, True),
                  "run loop vs legacy")
+
+
+def _digests(drive):
+    """{call label: digest of its snapshot}, in the form the fixture holds:
+    sha256 of each array's bytes, floats as float.hex strings."""
+    out = {}
+    for label, s in drive:
+        d = {k: hashlib.sha256(np.ascontiguousarray(s[k]).tobytes()).hexdigest()
+             for k in STATE + ["counters"]}
+        d["batch_counter"] = int(s["batch_counter"])
+        d["ret"] = [float(v).hex() for v in s["ret"]]
+        d["costs"] = [float(v).hex() for v in s["costs"]]
+        out[label] = d
+    return out
+
+
+@pytest.mark.parametrize("legacy", [True, False], ids=["legacy", "run"])
+@pytest.mark.parametrize("timing", [False, True], ids=["bb", "timing"])
+@pytest.mark.parametrize("name", CASES)
+def test_matches_parent_digests(name, timing, legacy):
+    """Both drivers compute, to the bit, what the legacy driver computed
+    when each driver still had its own copy of the kernels' text."""
+    fixture = json.loads(DIGESTS.read_text())
+    want = fixture["digests"][f"{name}-{'timing' if timing else 'bb'}"]
+    got = _digests(_drive(name, timing, legacy))
+    assert list(got) == list(want)
+    # keys that two recordings of the parent disagreed on are left out
+    keys = set(got["hot8"]) - set(fixture["left_out"])
+    for label in want:
+        assert set(want[label]) == keys, label
+        for k, v in want[label].items():
+            assert got[label][k] == v, f"{label}: {k}: {got[label][k]} != {v}"
+
+
+def test_pinned_blocks_stay():
+    """tseng_fixed drives the `fixed` branches of propose: the pinned
+    blocks never move, on either driver, while the others do."""
+    ids, x, y, slot = _pins("tseng_fixed")
+    free = np.ones(_case("tseng_fixed")[1].num_blocks, dtype=bool)
+    free[ids] = False
+    for timing in (False, True):
+        for legacy in (True, False):
+            drive = _drive("tseng_fixed", timing, legacy)
+            for label, s in drive:
+                assert np.array_equal(s["t_bx"][ids], x), label
+                assert np.array_equal(s["t_by"][ids], y), label
+                assert np.array_equal(s["t_bslot"][ids], slot), label
+            first, last = drive[0][1], drive[-1][1]
+            assert ((first["t_bx"] != last["t_bx"]) |
+                    (first["t_by"] != last["t_by"]))[free].any()
+    # the pins are IO blocks that an unpinned run of the same seed moves
+    unpinned = dict(_drive("tseng", False, True))["mid_stop"]
+    assert ((unpinned["t_bx"][ids] != x) | (unpinned["t_by"][ids] != y) |
+            (unpinned["t_bslot"][ids] != slot)).any()
 
 
 def test_strip_confines_moves():
