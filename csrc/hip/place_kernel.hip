@@ -73,8 +73,21 @@ struct MovesDev {
   int32_t* loc_claim;   // [gx*gy] the same, tile granularity
   int32_t* counters;    // [4]: attempts, accepted, winners, conflicts, over
                         // all batches of a run_batches call (host zeroes)
+  // stored costs [n_moves x cost_k]: what propose found net_cost and
+  // net_tcost of an accepted single move's nets to be after the move.
+  // Slot k is the k-th net of blk, slot nets(blk) + k the k-th of other;
+  // the slot of a net of other that blk has too holds COST_NONE.
+  float* mv_ncost;
+  float* mv_ntcost;     // written and read only when timing_tradeoff > 0
+  int32_t cost_k;       // <= 64
   int32_t n_moves;
 };
+
+// mv_to bit of a single move whose costs are not stored (more nets than
+// cost_k): apply recomputes them. Tile codes stay below it (host-checked).
+#define MV_RECOMPUTE (1 << 30)
+// no bb cost is negative (net_q >= 1, span >= 2)
+#define COST_NONE (-1.0f)
 
 // what one batch's propose is run with
 struct Sched {
@@ -124,9 +137,22 @@ struct MacroPos {
   }
 };
 
-// bb cost of net n with its members at `pos`
+// ---- pinned arithmetic ------------------------------------------------
+// The digests of tests/golden pin these bits, so the roundings are spelled
+// out and do not depend on what the compiler contracts (docs/KERNELS.md,
+// placer section, "bit-exactness rules"):
+//   cached cost   q * span, rounded            (mul_rn)
+//   bb delta      fma(q, span, -net_cost[n])   (one rounding)
+//   timing chain  t = fma(crit, delay, t) over the sinks in CSR order
+//   td delta      t - net_tcost[n]
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+// half perimeter of net n's bounding box, its members at `pos`
 template <class Pos> __device__ __forceinline__
-float net_bb_cost(const PlaceDev& p, int n, const Pos& pos) {
+int net_span(const PlaceDev& p, int n, const Pos& pos) {
   int xmin = 1 << 28, xmax = -1, ymin = 1 << 28, ymax = -1;
   int32_t e0 = p.net_blk_ptr[n], e1 = p.net_blk_ptr[n + 1];
   for (int32_t e = e0; e < e1; ++e) {
@@ -136,7 +162,13 @@ float net_bb_cost(const PlaceDev& p, int n, const Pos& pos) {
     xmin = min(xmin, x); xmax = max(xmax, x);
     ymin = min(ymin, y); ymax = max(ymax, y);
   }
-  return p.net_q[n] * ((xmax - xmin + 1) + (ymax - ymin + 1));
+  return (xmax - xmin + 1) + (ymax - ymin + 1);
+}
+
+// bb cost of net n with its members at `pos`
+template <class Pos> __device__ __forceinline__
+float net_bb_cost(const PlaceDev& p, int n, const Pos& pos) {
+  return mul_rn(p.net_q[n], (float)net_span(p, n, pos));
 }
 
 // timing cost of net n (sum over conns of crit * delay), members at `pos`
@@ -154,7 +186,8 @@ float net_td_cost(const PlaceDev& p, int n, const Pos& pos) {
     int x = p.bx[b], y = p.by[b];
     pos(p, b, x, y);
     int dx = abs(x - dx0), dy = abs(y - dy0);
-    t += p.conn_crit[c0 + (e - e0 - 1)] * p.delay_mat[dx * p.gy + dy];
+    t = __builtin_fmaf(p.conn_crit[c0 + (e - e0 - 1)],
+                       p.delay_mat[dx * p.gy + dy], t);
   }
   return t;
 }
@@ -175,12 +208,17 @@ bool blk_has_net(const PlaceDev& p, int32_t b, int32_t n) {
   return lo < p.blk_net_ptr[b + 1] && p.blk_nets[lo] == n;
 }
 
-// f(n) for each net n of block b, strided over the wave's lanes
+// f(k, n) for the k-th net n of block b, strided over the wave's lanes
+template <class F> __device__ __forceinline__
+void for_blk_nets_k(const PlaceDev& p, int32_t b, F f) {
+  const int32_t k0 = p.blk_net_ptr[b];
+  for (int32_t k = k0 + (threadIdx.x & 63); k < p.blk_net_ptr[b + 1]; k += 64)
+    f(k - k0, p.blk_nets[k]);
+}
+// f(n) for each net n of block b
 template <class F> __device__ __forceinline__
 void for_blk_nets(const PlaceDev& p, int32_t b, F f) {
-  for (int32_t k = p.blk_net_ptr[b] + (threadIdx.x & 63);
-       k < p.blk_net_ptr[b + 1]; k += 64)
-    f(p.blk_nets[k]);
+  for_blk_nets_k(p, b, [&](int32_t, int32_t n) { f(n); });
 }
 // f(j, n) for each net n of each member macro_blk[j] of a macro
 template <class F> __device__ __forceinline__
@@ -308,13 +346,171 @@ bool macro_shift_ok(const PlaceDev& p, const MacroPos& ms, int32_t mm0,
   return true;
 }
 
-// this lane's share of net n's exact delta under `pos`
+// net n's costs after a move, as refresh_net would cache them
+struct NetCosts { float bb, td; };
+
+// Adds this lane's share of net n's exact delta under `pos`; returns the
+// costs the delta was taken from.
 template <class Pos> __device__ __forceinline__
-void add_net_delta(const PlaceDev& p, int32_t n, const Pos& pos,
-                   float timing_tradeoff, float& dbb, float& dtd) {
-  dbb += net_bb_cost(p, n, pos) - p.net_cost[n];
-  if (timing_tradeoff > 0.0f)
-    dtd += net_td_cost(p, n, pos) - p.net_tcost[n];
+NetCosts add_net_delta(const PlaceDev& p, int32_t n, const Pos& pos,
+                       float timing_tradeoff, float& dbb, float& dtd) {
+  const float q = p.net_q[n], span = (float)net_span(p, n, pos);
+  NetCosts c{mul_rn(q, span), 0.0f};
+  dbb += __builtin_fmaf(q, span, -p.net_cost[n]);
+  if (timing_tradeoff > 0.0f) {
+    c.td = net_td_cost(p, n, pos);
+    dtd += c.td - p.net_tcost[n];
+  }
+  return c;
+}
+
+// ---- member-parallel evaluation of a single move ---------------------
+// The serial form above gives a lane a whole net: two dependent loads per
+// member, walked twice (bb, td), one member after the other. Here the
+// (net, member) pairs of all nets of blk and other are spread over the
+// lanes, 64 per pass, so the chain is a handful of loads deep whatever
+// the nets' sizes. Per-wave LDS staging; the waves of a workgroup take
+// different paths, so nothing here is a workgroup barrier.
+#define EVAL_SLOTS 64    // nets of blk and of other together
+#define EVAL_ITEMS 256   // members of those nets together
+struct EvalStage {
+  // per slot: slot k < nets(blk) is blk's k-th net, then other's nets
+  int32_t incl[EVAL_SLOTS];   // inclusive prefix sum of the member counts
+  int32_t e0[EVAL_SLOTS];     // net_blk_ptr[n]
+  int32_t c0[EVAL_SLOTS];     // net_sink_ptr[n]
+  int32_t drvx[EVAL_SLOTS], drvy[EVAL_SLOTS];   // driver after the move
+  int32_t xmin[EVAL_SLOTS], xmax[EVAL_SLOTS];
+  int32_t ymin[EVAL_SLOTS], ymax[EVAL_SLOTS];
+  // per item, sinks only: the factors of the timing chain
+  float crit[EVAL_ITEMS], delay[EVAL_ITEMS];
+};
+
+// orders this wave's LDS writes before its later LDS reads. A wave's LDS
+// instructions execute in issue order; this keeps the compiler to it.
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// What the two for_blk_nets_k loops of the single-move branch compute, to
+// the bit: lane k ends with dbb = 0 + delta(k-th net of blk) + delta(k-th
+// net of other, unless blk has it too), dtd likewise, and ca/cb hold those
+// two nets' costs after the move (cb.bb == COST_NONE for a shared net).
+// Needs n_a + n_b <= EVAL_SLOTS; returns false, with nothing touched, if
+// the nets have more than EVAL_ITEMS members together (wave-uniform).
+__device__ __forceinline__
+bool eval_move_parallel(const PlaceDev& p, EvalStage& st, const SwapPos& sw,
+                        int32_t blk, int32_t other, int n_a, int n_b,
+                        bool timing, float& dbb, float& dtd, NetCosts& ca,
+                        NetCosts& cb) {
+  const int lane = threadIdx.x & 63;
+  const int ns = n_a + n_b;
+  // this lane's slot
+  int32_t n = -1;
+  if (lane < n_a) n = p.blk_nets[p.blk_net_ptr[blk] + lane];
+  else if (lane < ns) n = p.blk_nets[p.blk_net_ptr[other] + lane - n_a];
+  // is a net of other also one of blk's? blk's slots are sorted: binary
+  // search through the lanes (range of at most 64: 7 halvings)
+  int lo = 0, hi = n_a;
+  for (int it = 0; it < 7; ++it) {
+    const int mid = (lo + hi) >> 1;
+    const int32_t v = __shfl(n, mid & 63);
+    if (lo < hi) { if (v < n) lo = mid + 1; else hi = mid; }
+  }
+  const int32_t found = __shfl(n, lo & 63);
+  const bool shared = lane >= n_a && lo < n_a && found == n;
+  const bool live = lane < ns && !shared;
+  int32_t e0 = 0, cnt = 0, c0 = 0;
+  int dx0 = 0, dy0 = 0;
+  float q = 0.0f, old_bb = 0.0f, old_td = 0.0f;
+  if (live) {
+    e0 = p.net_blk_ptr[n];
+    cnt = p.net_blk_ptr[n + 1] - e0;
+    q = p.net_q[n];
+    old_bb = p.net_cost[n];
+    if (timing) {
+      old_td = p.net_tcost[n];
+      c0 = p.net_sink_ptr[n];
+      const int32_t drv = p.net_blks[e0];
+      dx0 = p.bx[drv]; dy0 = p.by[drv];
+      sw(p, drv, dx0, dy0);
+    }
+  }
+  // items: slot 0's members, then slot 1's, ...
+  int incl = cnt;
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if (lane >= off) incl += v;
+  }
+  const int total = __shfl(incl, 63);
+  if (total > EVAL_ITEMS) return false;
+  st.incl[lane] = incl; st.e0[lane] = e0; st.c0[lane] = c0;
+  st.drvx[lane] = dx0; st.drvy[lane] = dy0;
+  st.xmin[lane] = 1 << 28; st.xmax[lane] = -1;
+  st.ymin[lane] = 1 << 28; st.ymax[lane] = -1;
+  wave_lds_sync();
+  for (int base = 0; base < total; base += 64) {
+    const int g = base + lane;
+    if (g >= total) continue;
+    // the item's slot: the first whose inclusive prefix exceeds g (shared
+    // and empty slots repeat their predecessor's prefix and are passed)
+    int s0 = 0, s1 = ns - 1;
+    for (int it = 0; it < 6; ++it) {
+      const int mid = (s0 + s1) >> 1;
+      const bool in_low = st.incl[mid] > g;
+      if (s0 < s1) { if (in_low) s1 = mid; else s0 = mid + 1; }
+    }
+    const int slot = s0;
+    const int mbr = g - (slot ? st.incl[slot - 1] : 0);
+    // every occurrence of a block in a net is an item of its own
+    const int32_t b = p.net_blks[st.e0[slot] + mbr];
+    int x = p.bx[b], y = p.by[b];
+    sw(p, b, x, y);
+    atomicMin(&st.xmin[slot], x); atomicMax(&st.xmax[slot], x);
+    atomicMin(&st.ymin[slot], y); atomicMax(&st.ymax[slot], y);
+    if (timing && mbr > 0) {
+      const int dx = abs(x - st.drvx[slot]), dy = abs(y - st.drvy[slot]);
+      st.crit[g] = p.conn_crit[st.c0[slot] + mbr - 1];
+      st.delay[g] = p.delay_mat[dx * p.gy + dy];
+    }
+  }
+  wave_lds_sync();
+  // back on the slot's lane: the net's costs and deltas, pinned roundings
+  NetCosts nc{COST_NONE, 0.0f};
+  float d_bb = 0.0f, d_td = 0.0f;
+  if (live) {
+    const float span = (float)((st.xmax[lane] - st.xmin[lane] + 1) +
+                               (st.ymax[lane] - st.ymin[lane] + 1));
+    nc.bb = mul_rn(q, span);
+    d_bb = __builtin_fmaf(q, span, -old_bb);
+    if (timing) {
+      // the chain runs left to right over the sinks in CSR order
+      float t = 0.0f;
+      const int i0 = incl - cnt;
+      for (int j = 1; j < cnt; ++j)
+        t = __builtin_fmaf(st.crit[i0 + j], st.delay[i0 + j], t);
+      nc.td = t;
+      d_td = t - old_td;
+    }
+  }
+  // lane k sums what the serial form gives it: slot k, then slot n_a + k
+  const int sb = (n_a + lane) & 63;
+  const float b_dbb = __shfl(d_bb, sb), b_dtd = __shfl(d_td, sb);
+  const float b_bb = __shfl(nc.bb, sb), b_td = __shfl(nc.td, sb);
+  if (lane < n_a) {
+    dbb += d_bb;
+    if (timing) dtd += d_td;
+    ca = nc;
+  }
+  if (lane < n_b) {
+    if (b_bb != COST_NONE) {
+      dbb += b_dbb;
+      if (timing) dtd += b_dtd;
+    }
+    cb = NetCosts{b_bb, b_td};
+  }
+  return true;
 }
 
 // Reduces the lanes' delta shares over the wave (dbb and dtd come back
@@ -323,8 +519,12 @@ __device__ __forceinline__
 bool metropolis(const Sched& s, int i, float& dbb, float& dtd) {
   dbb = wave_sum_f32(dbb);
   dtd = wave_sum_f32(dtd);
-  float delta = (1.0f - s.timing_tradeoff) * dbb * s.inv_bb_norm +
-                s.timing_tradeoff * dtd * s.inv_td_norm;
+  float delta;
+  {
+#pragma clang fp contract(off)
+    delta = (1.0f - s.timing_tradeoff) * dbb * s.inv_bb_norm +
+            s.timing_tradeoff * dtd * s.inv_td_norm;
+  }
   if (delta <= 0.0f) return true;
   if (s.T <= 0.0f) return false;
   float u = (rng_hash(s.seed, s.batch, i * 131 + 5) & 0xFFFFFF) *
@@ -415,18 +615,48 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
   // nets shared by both blocks are counted once (skipped in other's pass)
   const SwapPos sw{blk, x1, y1, other, other >= 0 ? x0 : -1000,
                    other >= 0 ? y0 : -1000};
-  for_blk_nets(p, blk, [&](int32_t n) {
-    add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
-  });
-  if (other >= 0)
-    for_blk_nets(p, other, [&](int32_t n) {
-      if (!blk_has_net(p, blk, n))
-        add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
+  const int n_a = p.blk_net_ptr[blk + 1] - p.blk_net_ptr[blk];
+  const int n_b =
+      other >= 0 ? p.blk_net_ptr[other + 1] - p.blk_net_ptr[other] : 0;
+  // the costs of this lane's net of blk (a) and of other (b) after the move
+  NetCosts ca{COST_NONE, 0.0f}, cb{COST_NONE, 0.0f};
+  // Member-parallel where the staging holds the move; else (wave-uniform)
+  // the serial form, a net per lane. Both give the same bits.
+  __shared__ EvalStage stage[PROP_WAVES];
+  const bool timing = s.timing_tradeoff > 0.0f;
+  bool evaluated = false;
+  if (n_a + n_b <= EVAL_SLOTS && (!timing || p.delay_mat != nullptr))
+    evaluated = eval_move_parallel(p, stage[threadIdx.x >> 6], sw, blk, other,
+                                   n_a, n_b, timing, dbb, dtd, ca, cb);
+  if (!evaluated) {
+    for_blk_nets_k(p, blk, [&](int32_t k, int32_t n) {
+      NetCosts nc = add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
+      if (k < 64) ca = nc;
     });
+    if (other >= 0)
+      for_blk_nets_k(p, other, [&](int32_t k, int32_t n) {
+        if (blk_has_net(p, blk, n)) return;
+        NetCosts nc = add_net_delta(p, n, sw, s.timing_tradeoff, dbb, dtd);
+        if (k < 64) cb = nc;
+      });
+  }
   if (!metropolis(s, i, dbb, dtd)) return;
+  // cost_k <= 64: a move that fits has every net in the lanes' first pass
+  const bool stored = n_a + n_b <= m.cost_k;
+  if (stored) {
+    const int64_t s0 = (int64_t)i * m.cost_k;
+    if (lane < n_a) m.mv_ncost[s0 + lane] = ca.bb;
+    if (lane < n_b) m.mv_ncost[s0 + n_a + lane] = cb.bb;
+    if (s.timing_tradeoff > 0.0f) {
+      if (lane < n_a) m.mv_ntcost[s0 + lane] = ca.td;
+      if (lane < n_b) m.mv_ntcost[s0 + n_a + lane] = cb.td;
+    }
+  }
   if (lane == 0) {
-    record_move(m, mv_from, i, blk, (x1 * p.gy + y1) * p.cap + slot1, other,
-                dbb, dtd, x0 * p.gy + y0);
+    record_move(m, mv_from, i, blk,
+                ((x1 * p.gy + y1) * p.cap + slot1) |
+                    (stored ? 0 : MV_RECOMPUTE),
+                other, dbb, dtd, x0 * p.gy + y0);
     c.take_loc(x0 * p.gy + y0);
     c.take_loc(x1 * p.gy + y1);
   }
@@ -438,8 +668,12 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
 // ---- resolve and apply, of a move as propose recorded it ------------
 struct Move {
   int32_t blk, other, to;
+  bool recompute;   // single move whose costs propose did not store
   __device__ __forceinline__ Move(const MovesDev& m, int i)
-      : blk(m.mv_blk[i]), other(m.mv_other[i]), to(m.mv_to[i]) {}
+      : blk(m.mv_blk[i]), other(m.mv_other[i]), to(m.mv_to[i]) {
+    recompute = !is_macro() && (to & MV_RECOMPUTE);
+    if (recompute) to &= ~MV_RECOMPUTE;
+  }
   __device__ __forceinline__ bool is_macro() const { return other <= -2; }
   __device__ __forceinline__ MacroPos macro() const {
     return MacroPos{-2 - other, (to >> 13) - 4096, (to & 0x1FFF) - 4096};
@@ -498,10 +732,12 @@ void refresh_net(const PlaceDev& p, int32_t n, const Pos& pos,
   if (timing_tradeoff > 0.0f) p.net_tcost[n] = net_td_cost(p, n, pos);
 }
 
-// Apply winner i. The net-cost refresh runs FIRST, lane-strided, with the
-// hypothetical positions over the PRE-move state (so lanes never read
-// positions another lane just wrote); duplicate refreshes of nets shared
-// by both blocks are idempotent. Then lane 0 commits grid and positions.
+// Apply winner i. The net costs come FIRST, lane-strided: a single move
+// copies what propose stored; a macro move, and a single move flagged
+// MV_RECOMPUTE, recompute them with the hypothetical positions over the
+// PRE-move state (so lanes never read positions another lane just wrote;
+// duplicate refreshes of nets shared by both blocks are idempotent). Both
+// give the same words. Then lane 0 commits grid and positions.
 __device__ __forceinline__
 void apply_move(const PlaceDev& p, const MovesDev& m, int i, const Move& mv,
                 float timing_tradeoff, double* cost_acc /*[2]: dbb, dtd*/) {
@@ -531,9 +767,26 @@ void apply_move(const PlaceDev& p, const MovesDev& m, int i, const Move& mv,
     int x0 = p.bx[blk], y0 = p.by[blk], s0 = p.bslot[blk];
     const SwapPos sw{blk, x1, y1, other, other >= 0 ? x0 : -1000,
                      other >= 0 ? y0 : -1000};
-    auto refresh = [&](int32_t n) { refresh_net(p, n, sw, timing_tradeoff); };
-    for_blk_nets(p, blk, refresh);
-    if (other >= 0) for_blk_nets(p, other, refresh);
+    if (mv.recompute) {
+      auto refresh = [&](int32_t n) { refresh_net(p, n, sw, timing_tradeoff); };
+      for_blk_nets(p, blk, refresh);
+      if (other >= 0) for_blk_nets(p, other, refresh);
+    } else {
+      // the costs propose stored, no member walk. A net of both blocks is
+      // written from blk's slot; other's slot of it holds COST_NONE.
+      const int64_t s0 = (int64_t)i * m.cost_k;
+      int32_t slot0 = 0;
+      auto copy = [&](int32_t k, int32_t n) {
+        const float bb = m.mv_ncost[s0 + slot0 + k];
+        if (bb == COST_NONE) return;
+        p.net_cost[n] = bb;
+        if (timing_tradeoff > 0.0f)
+          p.net_tcost[n] = m.mv_ntcost[s0 + slot0 + k];
+      };
+      for_blk_nets_k(p, blk, copy);
+      slot0 = p.blk_net_ptr[blk + 1] - p.blk_net_ptr[blk];
+      if (other >= 0) for_blk_nets_k(p, other, copy);
+    }
     if (lane == 0) {
       p.grid[((int64_t)x0 * p.gy + y0) * p.cap + s0] = other >= 0 ? other : -1;
       p.grid[((int64_t)x1 * p.gy + y1) * p.cap + slot1] = blk;
@@ -705,6 +958,9 @@ struct PlaceLaunchArgs {
   int32_t* mv_from;
   unsigned long long* net_claim64; unsigned long long* loc_claim64;
   int32_t* run_ctrl;
+  // stored costs of accepted moves (see MovesDev)
+  float* mv_ncost; float* mv_ntcost;
+  int32_t cost_k;
 };
 
 static void unpack(const PlaceLaunchArgs* a, PlaceDev& p, MovesDev& m) {
@@ -728,6 +984,15 @@ static void unpack(const PlaceLaunchArgs* a, PlaceDev& p, MovesDev& m) {
   m.mv_dbb = a->mv_dbb; m.mv_dtd = a->mv_dtd; m.mv_flags = a->mv_flags;
   m.net_claim = a->net_claim; m.loc_claim = a->loc_claim;
   m.counters = a->counters; m.n_moves = a->n_moves;
+  m.mv_ncost = a->mv_ncost; m.mv_ntcost = a->mv_ntcost;
+  m.cost_k = a->cost_k;
+}
+
+// what both batch drivers need besides their claim words
+static bool batch_args_ok(const PlaceLaunchArgs* a) {
+  return a->mv_from && a->mv_ncost && a->mv_ntcost && a->cost_k >= 1 &&
+         a->cost_k <= 64 &&
+         (int64_t)a->gx * a->gy * a->cap < (int64_t)MV_RECOMPUTE;
 }
 
 static Sched sched(const PlaceLaunchArgs* a, uint32_t batch) {
@@ -736,7 +1001,7 @@ static Sched sched(const PlaceLaunchArgs* a, uint32_t batch) {
 }
 
 int pnr_place_batch(const PlaceLaunchArgs* a, void* stream) {
-  if (!a->mv_from || !a->net_claim || !a->loc_claim)
+  if (!batch_args_ok(a) || !a->net_claim || !a->loc_claim)
     return (int)hipErrorInvalidValue;
   PlaceDev p; MovesDev m;
   unpack(a, p, m);
@@ -764,7 +1029,8 @@ int pnr_place_batch(const PlaceLaunchArgs* a, void* stream) {
 int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
                   int32_t target_moves, int32_t n_batches, void* stream) {
   if (n_batches < 0 || (n_batches & 3) || first_batch == 0 ||
-      !a->mv_from || !a->net_claim64 || !a->loc_claim64 || !a->run_ctrl)
+      !batch_args_ok(a) || !a->net_claim64 || !a->loc_claim64 ||
+      !a->run_ctrl)
     return (int)hipErrorInvalidValue;
   PlaceDev p; MovesDev m;
   unpack(a, p, m);

@@ -53,6 +53,9 @@ class PlaceLaunchArgs(ct.Structure):
         ("mv_from", ct.c_void_p),
         ("net_claim64", ct.c_void_p), ("loc_claim64", ct.c_void_p),
         ("run_ctrl", ct.c_void_p),
+        # stored costs of accepted moves, [n_moves x cost_k] each
+        ("mv_ncost", ct.c_void_p), ("mv_ntcost", ct.c_void_p),
+        ("cost_k", ct.c_int32),
     ]
 
 
@@ -226,6 +229,16 @@ class GpuPlacer:
             self.t_loc_claim64 = torch.zeros(gx * gy, dtype=torch.int64,
                                              device=device)
         self.t_mv_from = torch.zeros(nm, dtype=torch.int32, device=device)
+        # Costs that propose stores for commit, one slot per net of a move's
+        # two blocks. cost_k covers any two blocks of this netlist up to the
+        # 64 a wave holds in one pass; a move with more nets is recomputed
+        # by apply.
+        max_deg = int(np.diff(blk_net_ptr).max()) if nb else 0
+        self.cost_k = int(np.clip(2 * max_deg, 1, 64))
+        self.t_mv_ncost = torch.zeros(nm * self.cost_k, dtype=torch.float32,
+                                      device=device)
+        self.t_mv_ntcost = torch.zeros(nm * self.cost_k, dtype=torch.float32,
+                                       device=device)
         # counters [4] and the run loop's control block [4] (done, batches
         # executed, ticket, unused) share one buffer: one copy reads both
         self.t_run_state = torch.zeros(8, dtype=torch.int32, device=device)
@@ -391,6 +404,8 @@ class GpuPlacer:
             a.loc_claim64 = ptr(self.t_loc_claim64)
         a.mv_from = ptr(self.t_mv_from)
         a.run_ctrl = ptr(self.t_run_ctrl)
+        a.mv_ncost = ptr(self.t_mv_ncost); a.mv_ntcost = ptr(self.t_mv_ntcost)
+        a.cost_k = self.cost_k
         a.counters = ptr(self.t_counters); a.n_moves = self.n_moves
         a.T = T; a.rlim = max(1, int(rlim)); a.timing_tradeoff = tt
         a.inv_bb_norm = inv_bb; a.inv_td_norm = inv_td
