@@ -1,0 +1,246 @@
+// CDNA4 constrained multi-clock STA: the (source, sink) clock-pair analysis
+// of sta_kernel.hip's pnr_sta_analyze_domains with SDC false paths and
+// multicycle paths, shaped for the place and route loops: one launch per
+// level for all domains, no host round trip, nothing synchronised.
+//
+// Reference semantics: csrc/cpu/sta_serial.cpp analyze_domains (pair_skip /
+// pair_mult; do_timing_analysis_new's domain-pair loop, read_sdc.c). The
+// arithmetic per (block, domain) and per (connection, pair) is that of
+// sta_fwd_domain_level / sta_bwd_domain_level / sta_slack_domains, operation
+// for operation; only the launch shape and the data layout differ.
+//
+// Layout: arr[b * K + ci], req[b * R + row] (block-major, rows interleaved).
+// One thread per (block of the level, row) with the row fastest, so the K
+// (or R) lanes of one block read the same level_blocks / CSR / delay words
+// (one fetch per wave instead of one per domain launch) and their arr / req
+// words are adjacent, on the write and on every later gather.
+//
+// Every constraint comes from host tables (timing/constraints.py): the device
+// never multiplies a period by a multiplier, so there is no product for the
+// compiler to contract into the subtraction that follows it.
+#include "pnr_hip.h"
+
+namespace pnrh {
+
+struct StcDev {
+  const int32_t* level_blocks;
+  const int64_t* in_ptr;
+  const int64_t* in_conn;
+  const int64_t* out_ptr;
+  const int64_t* out_conn;
+  const int32_t* conn_driver;
+  const int32_t* conn_sink;
+  const uint8_t* is_seq;
+  const float* blk_delay;        // nullptr => T_clb
+  const int32_t* block_clock;    // per block, -1 = no domain
+  float T_clb, T_seq_out, T_seq_in, max_crit;
+  int32_t num_blocks, K, R;
+  int64_t num_conns;
+  const float* cons;             // [K*K] setup constraint per pair
+  const int32_t* pair_row;       // [K*K] backward row per pair
+  const uint8_t* skip;           // [K*K] false pair
+  const float* req_period;       // [R]
+  const int32_t* req_domain;     // [R]
+  float* arr;                    // [num_blocks * K]
+  float* req;                    // [num_blocks * R]
+};
+
+#define STC_NEG (-3.0e38f)
+#define STC_POS (3.0e38f)
+
+// forward, one level, all K source domains: thread -> (block i / K, ci % K)
+__global__ void stc_fwd_level(StcDev s, const float* __restrict__ delay,
+                              int32_t lv0, int32_t n) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)n * s.K) return;
+  int32_t i = (int32_t)(t / s.K);
+  int32_t ci = (int32_t)(t - (int64_t)i * s.K);
+  int32_t b = s.level_blocks[lv0 + i];
+  float* out = s.arr + (int64_t)b * s.K + ci;
+  if (s.is_seq[b]) {
+    *out = (s.block_clock[b] == ci) ? s.T_seq_out : STC_NEG;
+    return;
+  }
+  float m = STC_NEG;
+  for (int64_t k = s.in_ptr[b]; k < s.in_ptr[b + 1]; ++k) {
+    int64_t c = s.in_conn[k];
+    float v = s.arr[(int64_t)s.conn_driver[c] * s.K + ci];
+    if (v > STC_NEG) v += delay[c];
+    m = fmaxf(m, v);
+  }
+  float td = s.blk_delay ? s.blk_delay[b] : s.T_clb;
+  *out = (m > STC_NEG) ? m + td : STC_NEG;
+}
+
+// backward, one level, all R (sink domain, period) rows
+__global__ void stc_bwd_level(StcDev s, const float* __restrict__ delay,
+                              int32_t lv0, int32_t n) {
+  int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= (int64_t)n * s.R) return;
+  int32_t i = (int32_t)(t / s.R);
+  int32_t row = (int32_t)(t - (int64_t)i * s.R);
+  int32_t b = s.level_blocks[lv0 + i];
+  int32_t cj = s.req_domain[row];
+  float req_ep = s.req_period[row] - s.T_seq_in;
+  float m = STC_POS;
+  for (int64_t k = s.out_ptr[b]; k < s.out_ptr[b + 1]; ++k) {
+    int64_t c = s.out_conn[k];
+    int32_t snk = s.conn_sink[c];
+    float ri;
+    if (s.is_seq[snk]) {
+      ri = (s.block_clock[snk] == cj) ? req_ep : STC_POS;
+    } else {
+      float td = s.blk_delay ? s.blk_delay[snk] : s.T_clb;
+      float r = s.req[(int64_t)snk * s.R + row];
+      ri = (r < STC_POS) ? r - td : STC_POS;
+    }
+    if (ri < STC_POS) ri -= delay[c];
+    m = fminf(m, ri);
+  }
+  s.req[(int64_t)b * s.R + row] = m;
+}
+
+// one thread per (conn, ci, cj): worst slack / max criticality per conn and
+// the packed worst achieved period (see sta_slack_domains)
+__global__ void stc_pairs(StcDev s, const float* __restrict__ delay,
+                          float* slack, float* crit,
+                          unsigned long long* worst) {
+  const int64_t KK = (int64_t)s.K * s.K;
+  const int64_t total = s.num_conns * KK;
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    int64_t c = idx / KK;
+    int32_t pair = (int32_t)(idx - c * KK);
+    if (s.skip[pair]) continue;               // false path
+    int32_t ci = pair / s.K, cj = pair - ci * s.K;
+    int32_t drv = s.conn_driver[c];
+    int32_t snk = s.conn_sink[c];
+    float a = s.arr[(int64_t)drv * s.K + ci];
+    if (a <= STC_NEG) continue;
+    float constraint = s.cons[pair];
+    float ri;
+    if (s.is_seq[snk]) {
+      ri = (s.block_clock[snk] == cj) ? constraint - s.T_seq_in : STC_POS;
+    } else {
+      float td = s.blk_delay ? s.blk_delay[snk] : s.T_clb;
+      float r = s.req[(int64_t)snk * s.R + s.pair_row[pair]];
+      ri = (r < STC_POS) ? r - td : STC_POS;
+    }
+    if (ri >= STC_POS) continue;
+    float sl = ri - (a + delay[c]);
+    // min slack per conn: atomicMin on order-preserving bits
+    unsigned sb = __float_as_uint(sl);
+    sb = (sb & 0x80000000u) ? ~sb : (sb | 0x80000000u);
+    atomicMin((unsigned*)&slack[c], sb);
+    float cr = 1.0f - sl / constraint;
+    cr = fminf(fmaxf(cr, 0.0f), s.max_crit);
+    atomicMax((unsigned*)&crit[c], __float_as_uint(cr));  // cr >= 0
+    float achieved = constraint - sl;
+    unsigned long long packed =
+        ((unsigned long long)__float_as_uint(achieved / constraint) << 32) |
+        __float_as_uint(achieved);
+    atomicMax(worst, packed);
+  }
+}
+
+// decode the slack bits; thread 0 also decodes the worst word into the
+// float32 period: no analysed pair (high half 0) => periods[0]
+__global__ void stc_finish(int64_t num_conns, float* slack,
+                           const unsigned long long* worst,
+                           const float* __restrict__ req_period,
+                           float* period_out) {
+  int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0) {
+    unsigned long long w = *worst;
+    period_out[0] = (w >> 32) ? __uint_as_float((unsigned)(w & 0xFFFFFFFFull))
+                              : req_period[0];
+  }
+  for (; c < num_conns; c += (int64_t)gridDim.x * blockDim.x) {
+    unsigned sb = __float_as_uint(slack[c]);
+    if (sb == 0xFFFFFFFFu) { slack[c] = 0.0f; continue; }
+    sb = (sb & 0x80000000u) ? (sb & 0x7FFFFFFFu) : ~sb;
+    slack[c] = __uint_as_float(sb);
+  }
+}
+
+}  // namespace pnrh
+
+using namespace pnrh;
+
+extern "C" {
+
+struct StaConstrainedArgs {
+  const int32_t* level_blocks;
+  const int64_t* in_ptr; const int64_t* in_conn;
+  const int64_t* out_ptr; const int64_t* out_conn;
+  const int32_t* conn_driver; const int32_t* conn_sink;
+  const uint8_t* is_seq;
+  const float* blk_delay;        // nullptr => scalar T_clb
+  const int32_t* block_clock;
+  float T_clb, T_seq_out, T_seq_in, max_crit;
+  int32_t num_blocks, num_levels, K, R;
+  int64_t num_conns;
+  const float* cons; const int32_t* pair_row; const uint8_t* skip;
+  const float* req_period; const int32_t* req_domain;
+  float* arr; float* req;
+  const float* delay; float* slack; float* crit;
+  unsigned long long* worst_bits;   // [1]
+  float* period_out;                // [1]
+  const int32_t* level_start_host;  // host copy for launch bounds
+};
+
+int pnr_sta_constrained(const StaConstrainedArgs* a, void* stream) {
+  if (a->K < 1 || a->K > 64 || a->R < a->K || a->R > 2 * 64 * 64 ||
+      a->num_blocks < 0 || a->num_conns < 0 || a->num_levels < 0)
+    return (int)hipErrorInvalidValue;
+  StcDev s{a->level_blocks, a->in_ptr, a->in_conn, a->out_ptr, a->out_conn,
+           a->conn_driver, a->conn_sink, a->is_seq, a->blk_delay,
+           a->block_clock, a->T_clb, a->T_seq_out, a->T_seq_in, a->max_crit,
+           a->num_blocks, a->K, a->R, a->num_conns, a->cons, a->pair_row,
+           a->skip, a->req_period, a->req_domain, a->arr, a->req};
+  hipStream_t st = (hipStream_t)stream;
+  const int32_t* ls = a->level_start_host;
+  // the level table must partition [0, num_blocks): it bounds every launch
+  if (a->num_levels > 0 && (ls[0] != 0 || ls[a->num_levels] != a->num_blocks))
+    return (int)hipErrorInvalidValue;
+  hipError_t me;
+  me = hipMemsetAsync(a->worst_bits, 0, sizeof(unsigned long long), st);
+  if (me != hipSuccess) return (int)me;
+  // slack sentinel: all-ones encoded bits (= +inf in the ordering)
+  me = hipMemsetAsync(a->slack, 0xFF, a->num_conns * sizeof(float), st);
+  if (me != hipSuccess) return (int)me;
+  me = hipMemsetAsync(a->crit, 0, a->num_conns * sizeof(float), st);
+  if (me != hipSuccess) return (int)me;
+  for (int lv = 0; lv < a->num_levels; ++lv) {
+    int n = ls[lv + 1] - ls[lv];
+    if (n <= 0) continue;
+    int64_t th = (int64_t)n * a->K;
+    hipLaunchKernelGGL(stc_fwd_level, dim3((unsigned)((th + 255) / 256)),
+                       dim3(256), 0, st, s, a->delay, ls[lv], n);
+  }
+  for (int lv = a->num_levels - 1; lv >= 0; --lv) {
+    int n = ls[lv + 1] - ls[lv];
+    if (n <= 0) continue;
+    int64_t th = (int64_t)n * a->R;
+    hipLaunchKernelGGL(stc_bwd_level, dim3((unsigned)((th + 255) / 256)),
+                       dim3(256), 0, st, s, a->delay, ls[lv], n);
+  }
+  int64_t total = a->num_conns * (int64_t)a->K * a->K;
+  int64_t g64 = (total + 255) / 256;
+  int grid = (int)(g64 < 2048 ? g64 : 2048);
+  if (grid > 0)
+    hipLaunchKernelGGL(stc_pairs, dim3(grid), dim3(256), 0, st, s, a->delay,
+                       a->slack, a->crit, a->worst_bits);
+  int64_t c64 = (a->num_conns + 255) / 256;
+  int cgrid = (int)(c64 < 2048 ? c64 : 2048);
+  if (cgrid < 1) cgrid = 1;  // the period is decoded even without connections
+  hipLaunchKernelGGL(stc_finish, dim3(cgrid), dim3(256), 0, st, a->num_conns,
+                     a->slack, a->worst_bits, a->req_period, a->period_out);
+  return (int)hipGetLastError();
+}
+
+int64_t pnr_sta_constrained_args_sizeof() {
+  return (int64_t)sizeof(StaConstrainedArgs);
+}
+
+}  // extern "C"

@@ -71,6 +71,15 @@ def build_parser():
     # outputs
     p.add_argument("--sdc", type=str, default=None,
                    help="SDC constraints (create_clock -period, subset)")
+    p.add_argument("--sdc_driven", action="store_true",
+                   help="place and route against the --sdc constraints: the "
+                        "loops' timing engine analyses every (source, sink) "
+                        "clock pair at its own period, skips false paths and "
+                        "widens multicycle paths (--sta_engine cpu and gpu "
+                        "alike; needs --sdc and a netlist with clock "
+                        "domains). Each router iteration's cpd in the log "
+                        "and the stats history is then the worst achieved "
+                        "period; the final reports keep the CPU engine")
     p.add_argument("--draw_place", type=str, default=None,
                    help="render the placement to SVG (headless draw.c)")
     p.add_argument("--draw_route", type=str, default=None,
@@ -134,6 +143,10 @@ def main(argv=None):
         args = apply_settings(parser, args, argv)
     if args.sta_engine == "gpu" and args.engine != "gpu":
         parser.error("--sta_engine gpu requires --engine gpu")
+    if args.sdc_driven and not args.sdc:
+        parser.error("--sdc_driven requires --sdc")
+    if args.sdc_driven and args.router_algorithm != "timing_driven":
+        parser.error("--sdc_driven requires --router_algorithm timing_driven")
     from .arch.archdef import get_arch
     from .arch.xml_parser import parse_arch_xml, size_grid_for_netlist
     from .io.synth import synth_netlist, spec_for_arch
@@ -186,7 +199,7 @@ def main(argv=None):
     # sta_loop: what the placer and the router refresh timing with
     sta = STA(netlist, arch) if timing else None
     sta_loop = sta
-    if timing and args.sta_engine == "gpu":
+    if timing and args.sta_engine == "gpu" and not args.sdc_driven:
         sta_loop = loop_sta(netlist, arch, args.engine, args.sta_engine)
     sdc_clocks = {}
     sdc_all = None
@@ -201,6 +214,20 @@ def main(argv=None):
             print(f"SDC: false path {f_ or '*'} -> {t_ or '*'}")
         for (f_, t_, n_) in sdc_all["multicycle"]:
             print(f"SDC: multicycle {n_} {f_ or '*'} -> {t_ or '*'}")
+    if args.sdc_driven:
+        from .timing.constraints import constraints_from_sdc
+        try:
+            cons = constraints_from_sdc(sdc_all, netlist)
+            sta_loop = loop_sta(netlist, arch, args.engine, args.sta_engine,
+                                constraints=cons)
+        except ValueError as e:
+            print(f"error: --sdc_driven: {e}", file=sys.stderr)
+            return 2
+        n_false = int(sta_loop.plan.skip.sum())
+        n_multi = int((sta_loop.plan.mult != 1).sum())
+        print(f"SDC-driven: {sta_loop.plan.K} domains, {n_false} false "
+              f"pairs, {n_multi} multicycle pairs (loop cpd = worst "
+              f"achieved period)")
 
     # ---- placement ----
     t0 = time.perf_counter()
@@ -357,14 +384,8 @@ def main(argv=None):
                 if hasattr(res.router, "sink_delays") \
                 else res.router.t_sink_delay.cpu().numpy()
             cd3 = cmap3.conn_delays(sd3)
-            cnames = getattr(netlist, "clock_names", []) or []
-            periods = [sdc_clocks.get(c, list(sdc_clocks.values())[0])
-                       for c in cnames] or list(sdc_clocks.values())[:1]
-            bc = getattr(netlist, "block_clock")
-            ps = pm = None
-            if sdc_all and (sdc_all["false_paths"] or sdc_all["multicycle"]):
-                from .timing.report import pair_constraints
-                ps, pm = pair_constraints(sdc_all, cnames)
+            from .timing.constraints import constraints_from_sdc
+            bc, periods, ps, pm = constraints_from_sdc(sdc_all, netlist)
             wp, sl, cr = sta.analyze_domains(cd3, bc, periods,
                                              pair_skip=ps, pair_mult=pm)
             ok_sdc = all(wp <= p_ * (1 + 1e-6) for p_ in periods[:1])

@@ -24,11 +24,24 @@ class FlowResult:
     times: dict = field(default_factory=dict)
 
 
-def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu"):
+def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu",
+             constraints=None):
     """The STA engine the place and route loops refresh timing with.
     "gpu" is GpuSTA(max_crit=1.0): unclamped, so the placer sees what the
-    CPU engine gives it, and the router clamps through max_criticality."""
+    CPU engine gives it, and the router clamps through max_criticality.
+
+    constraints: None, or clock-pair constraints (timing.constraints.
+    Constraints, a dict with its keys, or a (block_clock, periods,
+    pair_skip, pair_mult) tuple). With them the engine is ConstrainedSTA
+    ("cpu") or GpuConstrainedSTA over that GpuSTA ("gpu"), and the loops'
+    cpd is the worst achieved period."""
+    if constraints is not None:
+        from .timing.constraints import as_constraints
+        constraints = as_constraints(constraints)
     if sta_engine == "cpu":
+        if constraints is not None:
+            from .timing.sta import ConstrainedSTA
+            return ConstrainedSTA(netlist, arch, *constraints)
         return STA(netlist, arch)
     if sta_engine != "gpu":
         raise ValueError(f"sta_engine must be 'cpu' or 'gpu', "
@@ -36,20 +49,25 @@ def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu"):
     if engine != "gpu":
         raise ValueError("sta_engine='gpu' needs engine='gpu'")
     from .timing.gpu_sta import GpuSTA
+    if constraints is not None:
+        from .timing.gpu_sta import GpuConstrainedSTA
+        return GpuConstrainedSTA(GpuSTA(netlist, arch, max_crit=1.0),
+                                 *constraints)
     return GpuSTA(netlist, arch, max_crit=1.0)
 
 
 def run_flow(arch_name: str = "tseng", seed: int = 1, timing_driven: bool = True,
              fill: float = 0.75, max_route_iters: int = 60, verbose: bool = False,
              engine: str = "cpu", netlist=None, arch: ArchDef = None,
-             sta_engine: str = "cpu"):
+             sta_engine: str = "cpu", constraints=None):
     """sta_engine: "cpu" (timing.sta.STA) or "gpu" (GpuSTA and the
-    device-resident timing loop; needs engine="gpu")."""
+    device-resident timing loop; needs engine="gpu"). constraints: see
+    loop_sta; None runs the single-clock engines."""
     arch = arch or get_arch(arch_name)
     if netlist is None:
         netlist = synth_netlist(spec_for_arch(arch, fill=fill, seed=seed))
-    sta = loop_sta(netlist, arch, engine, sta_engine) if timing_driven \
-        else None
+    sta = loop_sta(netlist, arch, engine, sta_engine, constraints) \
+        if timing_driven else None
     times = {}
     t0 = time.perf_counter()
     placement = anneal_place(netlist, arch, seed=seed,

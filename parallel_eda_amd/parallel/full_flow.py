@@ -19,7 +19,8 @@ import numpy as np
 def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
                  device="cuda:0", seed=7, timing_driven=True,
                  max_route_iters=80, incremental=True, verbose=False,
-                 inner_num=1.0, check=False, sta_engine="cpu"):
+                 inner_num=1.0, check=False, sta_engine="cpu",
+                 constraints=None):
     """One complete GPU place+route flow to feasibility (the headline
     benchmark step). The rr graph g (and optionally its device-resident
     upload dev_graph) is the fixed device model — passed in, like the
@@ -29,6 +30,11 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
     sta_engine: "cpu" (timing.sta.STA, host refresh) or "gpu" (GpuSTA
     with the device-resident timing loop in the single-GPU anneal and the
     route loop; the strip-sharded multi-GPU anneal keeps the CPU engine).
+
+    constraints: None, or clock-pair constraints as flow.loop_sta takes
+    them: the single-GPU anneal and the route loop then run ConstrainedSTA
+    ("cpu") or GpuConstrainedSTA ("gpu") and cpd is the worst achieved
+    period; the strip-sharded anneal keeps the unconstrained CPU engine.
 
     Returns dict(place, route, wirelength, cpd, success, phase_s) —
     rank-identical."""
@@ -49,6 +55,15 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
         # unclamped, like the CPU engine: the route loop clamps through
         # its own max criticality
         loop_sta = GpuSTA(netlist, arch, device=device, max_crit=1.0)
+    if timing_driven and constraints is not None:
+        from ..timing.constraints import as_constraints
+        cons = as_constraints(constraints)
+        if sta_engine == "gpu":
+            from ..timing.gpu_sta import GpuConstrainedSTA
+            loop_sta = GpuConstrainedSTA(loop_sta, *cons)
+        else:
+            from ..timing.sta import ConstrainedSTA
+            loop_sta = ConstrainedSTA(netlist, arch, *cons)
     tt = 0.5 if timing_driven else 0.0
 
     t0 = time.perf_counter()

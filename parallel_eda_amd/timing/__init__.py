@@ -1,3 +1,3 @@
-from .sta import STA
+from .sta import STA, ConstrainedSTA
 
-__all__ = ["STA"]
+__all__ = ["STA", "ConstrainedSTA"]

@@ -41,9 +41,39 @@ class StaDomainsArgs(ct.Structure):
     ]
 
 
+class StaConstrainedArgs(ct.Structure):
+    _fields_ = [
+        ("level_blocks", ct.c_void_p),
+        ("in_ptr", ct.c_void_p), ("in_conn", ct.c_void_p),
+        ("out_ptr", ct.c_void_p), ("out_conn", ct.c_void_p),
+        ("conn_driver", ct.c_void_p), ("conn_sink", ct.c_void_p),
+        ("is_seq", ct.c_void_p), ("blk_delay", ct.c_void_p),
+        ("block_clock", ct.c_void_p),
+        ("T_clb", ct.c_float), ("T_seq_out", ct.c_float),
+        ("T_seq_in", ct.c_float), ("max_crit", ct.c_float),
+        ("num_blocks", ct.c_int32), ("num_levels", ct.c_int32),
+        ("K", ct.c_int32), ("R", ct.c_int32),
+        ("num_conns", ct.c_int64),
+        ("cons", ct.c_void_p), ("pair_row", ct.c_void_p),
+        ("skip", ct.c_void_p),
+        ("req_period", ct.c_void_p), ("req_domain", ct.c_void_p),
+        ("arr", ct.c_void_p), ("req", ct.c_void_p),
+        ("delay", ct.c_void_p), ("slack", ct.c_void_p), ("crit", ct.c_void_p),
+        ("worst_bits", ct.c_void_p), ("period_out", ct.c_void_p),
+        ("level_start_host", ct.c_void_p),
+    ]
+
+
 def _lib():
     lib = hip_api.lib()
     if not hasattr(lib, "_sta_ready"):
+        lib.pnr_sta_constrained.restype = ct.c_int
+        lib.pnr_sta_constrained.argtypes = [ct.POINTER(StaConstrainedArgs),
+                                            ct.c_void_p]
+        lib.pnr_sta_constrained_args_sizeof.restype = ct.c_int64
+        if lib.pnr_sta_constrained_args_sizeof() != \
+                ct.sizeof(StaConstrainedArgs):
+            raise RuntimeError("StaConstrainedArgs ABI mismatch")
         lib.pnr_sta_analyze.restype = ct.c_int
         lib.pnr_sta_analyze.argtypes = [ct.POINTER(StaLaunchArgs), ct.c_void_p]
         lib.pnr_sta_args_sizeof.restype = ct.c_int64
@@ -135,7 +165,8 @@ class GpuSTA:
         hip_api.check(rc, "sta_analyze")
         return self.t_cpd, self.t_slack, self.t_crit
 
-    def analyze_domains(self, conn_delay, block_clock, periods):
+    def analyze_domains(self, conn_delay, block_clock, periods,
+                        pair_skip=None, pair_mult=None):
         """Multi-clock analysis on the device (reference:
         do_timing_analysis_new's (src,sink)-domain-pair loop). Returns
         (worst_achieved_period, slack[], crit[]), equal to the CPU
@@ -144,7 +175,16 @@ class GpuSTA:
         period of the largest achieved/constraint ratio, tracked as one
         packed 64-bit max; among equal ratios the larger period wins
         (the CPU engine keeps the first it meets). With no analysable
-        (source, sink) pair both engines return periods[0]."""
+        (source, sink) pair both engines return periods[0].
+
+        pair_skip / pair_mult: KxK false-pair and multicycle arrays as in
+        STA.analyze_domains. With either given the analysis runs through a
+        temporary GpuConstrainedSTA (pnr_sta_constrained); with both None
+        it is pnr_sta_analyze_domains, the second implementation the
+        constrained kernels are compared with."""
+        if pair_skip is not None or pair_mult is not None:
+            return GpuConstrainedSTA(self, block_clock, periods, pair_skip,
+                                     pair_mult).analyze(conn_delay)
         torch = self.torch
         K = len(periods)
         nb = self.netlist.num_blocks
@@ -213,3 +253,140 @@ class GpuSTA:
         torch.cuda.synchronize(self.device)
         return (float(self.t_cpd.item()), self.t_slack.cpu().numpy(),
                 self.t_crit.cpu().numpy())
+
+
+class GpuConstrainedSTA:
+    """Multi-clock analysis under false-path and multicycle constraints as
+    a loop engine (csrc/hip/sta_constrained.hip): analyze_device() takes a
+    device delay tensor and leaves the worst achieved period, slack and
+    crit on the device with no allocation, host copy or synchronisation,
+    so timing.device_loop drives it like a GpuSTA.
+
+    It shares the graph tensors of `gsta`, clamps crit with its max_crit
+    and owns everything it writes: arr[nb*K] and req[nb*R] (block-major:
+    the rows of one block are adjacent; arr_rows()/req_rows() give them
+    row by row), slack, crit, the packed worst word, the float32[1]
+    period, and the uploaded constraint_plan and block_clock. Results
+    equal STA.analyze_domains(..., pair_skip, pair_mult) bit for bit (crit
+    up to the max_crit clamp; the worst period up to GpuSTA.analyze_domains'
+    tie rule)."""
+
+    def __init__(self, gsta, block_clock, periods, pair_skip=None,
+                 pair_mult=None):
+        from .constraints import constraint_plan, check_block_clock
+        torch = gsta.torch
+        self.torch = torch
+        self.gsta = gsta
+        self.device = gsta.device
+        self.arch = gsta.arch
+        self.netlist = gsta.netlist
+        self.max_crit = gsta.max_crit
+        self.plan = plan = constraint_plan(periods, pair_skip, pair_mult)
+        nb = self.netlist.num_blocks
+        nc = self.netlist.num_conns
+        bc = check_block_clock(block_clock, nb, plan.K)
+        self.K, self.R = plan.K, plan.R
+        if gsta.level_start_host[0] != 0 or \
+                gsta.level_start_host[gsta.num_levels] != nb:
+            raise ValueError("GpuSTA level table does not cover the blocks")
+        self.t_conn_driver = gsta.t_conn_driver
+        self.t_conn_sink = gsta.t_conn_sink
+
+        def up(a):
+            return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+        def buf(n, dtype=torch.float32):
+            return torch.zeros(n, dtype=dtype, device=self.device)
+
+        self.t_block_clock = up(bc)
+        self.t_cons = up(plan.cons)
+        self.t_pair_row = up(plan.pair_row)
+        self.t_skip = up(plan.skip)
+        self.t_req_period = up(plan.req_period)
+        self.t_req_domain = up(plan.req_domain)
+        self.t_arr = buf(nb * plan.K)
+        self.t_req = buf(nb * plan.R)
+        self.t_slack = buf(nc)
+        self.t_crit = buf(nc)
+        # (ratio bits << 32) | achieved-period bits, see stc_pairs
+        self.t_worst = buf(1, torch.int64)
+        self.t_period = buf(1)
+        self.lib = _lib()
+        self._args = self._build_args()
+
+    @property
+    def num_conns(self):
+        return self.netlist.num_conns
+
+    def owned_buffers(self):
+        """Every tensor analyze_device writes."""
+        return (self.t_arr, self.t_req, self.t_slack, self.t_crit,
+                self.t_worst, self.t_period)
+
+    def _build_args(self):
+        g = self.gsta
+        a = StaConstrainedArgs()
+        pt = lambda t: ct.c_void_p(t.data_ptr())
+        a.level_blocks = pt(g.t_level_blocks)
+        a.in_ptr = pt(g.t_in_ptr); a.in_conn = pt(g.t_in_conn)
+        a.out_ptr = pt(g.t_out_ptr); a.out_conn = pt(g.t_out_conn)
+        a.conn_driver = pt(g.t_conn_driver)
+        a.conn_sink = pt(g.t_conn_sink)
+        a.is_seq = pt(g.t_is_seq)
+        a.blk_delay = (pt(g.t_blk_delay)
+                       if g.t_blk_delay is not None else None)
+        a.block_clock = pt(self.t_block_clock)
+        a.T_clb = self.arch.T_clb; a.T_seq_out = self.arch.T_seq_out
+        a.T_seq_in = self.arch.T_seq_in; a.max_crit = self.max_crit
+        a.num_blocks = self.netlist.num_blocks
+        a.num_levels = g.num_levels
+        a.K = self.K; a.R = self.R
+        a.num_conns = self.netlist.num_conns
+        a.cons = pt(self.t_cons); a.pair_row = pt(self.t_pair_row)
+        a.skip = pt(self.t_skip)
+        a.req_period = pt(self.t_req_period)
+        a.req_domain = pt(self.t_req_domain)
+        a.arr = pt(self.t_arr); a.req = pt(self.t_req)
+        a.slack = pt(self.t_slack); a.crit = pt(self.t_crit)
+        a.worst_bits = pt(self.t_worst); a.period_out = pt(self.t_period)
+        a.level_start_host = g.level_start_host.ctypes.data_as(ct.c_void_p)
+        return a
+
+    def analyze_device(self, t_conn_delay):
+        """Device path: conn delays in, (period_t, slack_t, crit_t) out, all
+        device tensors of this engine, valid in stream order."""
+        t = t_conn_delay
+        if (not t.is_cuda or t.dtype != self.torch.float32
+                or t.numel() != self.netlist.num_conns
+                or not t.is_contiguous()):
+            raise ValueError("analyze_device: need a contiguous device "
+                             f"float32 tensor of {self.netlist.num_conns} "
+                             "connection delays")
+        self._args.delay = ct.c_void_p(t.data_ptr())
+        stream = self.torch.cuda.current_stream().cuda_stream
+        rc = self.lib.pnr_sta_constrained(ct.byref(self._args), stream)
+        hip_api.check(rc, "sta_constrained")
+        return self.t_period, self.t_slack, self.t_crit
+
+    def analyze(self, conn_delay):
+        """Host-compatible API (numpy in/out): (worst_achieved_period,
+        slack[], crit[])."""
+        torch = self.torch
+        t_delay = torch.from_numpy(
+            np.ascontiguousarray(conn_delay, dtype=np.float32)).to(self.device)
+        self.analyze_device(t_delay)
+        torch.cuda.synchronize(self.device)
+        return (float(self.t_period.item()), self.t_slack.cpu().numpy(),
+                self.t_crit.cpu().numpy())
+
+    def arr_rows(self):
+        """Arrival per (source domain, block), numpy [K, num_blocks]."""
+        nb = self.netlist.num_blocks
+        return np.ascontiguousarray(
+            self.t_arr.cpu().numpy().reshape(nb, self.K).T)
+
+    def req_rows(self):
+        """Required time per (backward row, block), numpy [R, num_blocks]."""
+        nb = self.netlist.num_blocks
+        return np.ascontiguousarray(
+            self.t_req.cpu().numpy().reshape(nb, self.R).T)

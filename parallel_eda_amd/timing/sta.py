@@ -64,3 +64,37 @@ class STA:
         wp, slack, crit = self.tg.analyze_domains(conn_delay, bc, pr,
                                                   pair_skip, pair_mult)
         return float(wp), np.asarray(slack), np.asarray(crit)
+
+
+class ConstrainedSTA(STA):
+    """The place and route loops' CPU engine under clock-pair constraints:
+    analyze() is analyze_domains with the stored block_clock, periods,
+    false pairs and multicycle multipliers. The "cpd" it returns is the
+    worst achieved period (the achieved period of the pair with the
+    largest achieved/constraint ratio; periods[0] if no pair is
+    analysable), slack the minimum and crit the maximum over the analysed
+    pairs, each pair's crit normalised by its own constraint."""
+
+    def __init__(self, netlist, arch: ArchDef, block_clock, periods,
+                 pair_skip=None, pair_mult=None):
+        from .constraints import constraint_plan, check_block_clock
+        super().__init__(netlist, arch)
+        self.plan = constraint_plan(periods, pair_skip, pair_mult)
+        self.block_clock = check_block_clock(block_clock, netlist.num_blocks,
+                                             self.plan.K)
+        self.periods = self.plan.periods
+        K = self.plan.K
+        self.pair_skip = (None if pair_skip is None
+                          else self.plan.skip.reshape(K, K))
+        self.pair_mult = (None if pair_mult is None
+                          else self.plan.mult.reshape(K, K))
+
+    @property
+    def num_conns(self):
+        return self.netlist.num_conns
+
+    def analyze(self, conn_delay):
+        """Returns (worst_achieved_period, slack[], crit[])."""
+        return self.analyze_domains(conn_delay, self.block_clock,
+                                    self.periods, self.pair_skip,
+                                    self.pair_mult)

@@ -1,0 +1,597 @@
+"""Constrained multi-clock timing engines: timing/constraints.py,
+timing.sta.ConstrainedSTA and timing.gpu_sta.GpuConstrainedSTA
+(csrc/hip/sta_constrained.hip).
+
+Oracles:
+
+* the CPU engine, `STA.analyze_domains(..., pair_skip, pair_mult)`;
+* `replay`: a numpy float32 replay of the device algorithm from the host
+  plan (`constraint_plan`): level sweeps over the K forward and R backward
+  rows from `level_arrays()` / `csr_arrays()`, then the pair pass reading
+  the `cons` / `pair_row` / `skip` tables. It is checked on the CPU to equal
+  the CPU engine bit for bit (slack, crit and, with the CPU engine's
+  first-met rule replayed, the worst period), which proves the plan without
+  a GPU; it is the only oracle for the device `arr` / `req` rows.
+
+Every value is a chain of single fp32 `+`, `-`, `max`, `min` and one
+correctly rounded division per (connection, pair); the one product,
+period * multiplier, is rounded on the host. So everything is held to bit
+equality; the only freedom is the worst period among equal
+achieved/constraint ratios (the device keeps the larger period, the CPU
+engine the first it meets).
+
+The graphs, delays and the three-domain set-up are those of
+tests/test_sta_exact.py.
+"""
+import functools
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+
+from parallel_eda_amd.io.synth import NetlistPy
+from parallel_eda_amd.timing.constraints import (constraint_plan,
+                                                 check_block_clock)
+from parallel_eda_amd.timing.sta import STA, ConstrainedSTA
+
+from test_sta_exact import (case, domains, _same_bits, _ragged, _consts, F,
+                            K, ONE_PASS)
+
+gpu = pytest.mark.gpu
+
+NEG, POS = F(-3.0e38), F(3.0e38)
+CPU_GRAPHS = ("wide", "wide_het", "mid", "stride", "chain", "idle_ff")
+GPU_GRAPHS = ("wide", "wide_het", "mid", "stride")
+SETS = ("none", "false01", "false_row", "all_false", "mc01", "mc_shared",
+        "false_and_mc")
+
+
+def constraint_set(name, k=K):
+    """(pair_skip, pair_mult) of one named set; None where the set has no
+    false pair / no multicycle pair."""
+    skip = np.zeros((k, k), np.uint8)
+    mult = np.ones((k, k), F)
+    if name == "none":
+        return None, None
+    if name == "false01":
+        skip[0, 1] = 1
+        return skip, None
+    if name == "false_row":
+        skip[0, :] = 1
+        return skip, None
+    if name == "all_false":
+        skip[:] = 1
+        return skip, None
+    if name == "mc01":
+        mult[0, 1] = 2
+        return None, mult
+    if name == "mc_shared":     # one shared extra row and a self pair
+        mult[0, 1] = 2
+        mult[2, 1] = 2
+        mult[1, 1] = 3
+        return None, mult
+    if name == "false_and_mc":
+        skip[0, 1] = 1
+        mult[0, 1] = 2
+        return skip, mult
+    raise KeyError(name)
+
+
+def setup_of(name):
+    """block_clock, periods and delays of one graph: domains() for the
+    graphs it knows, the same rule for the small ones."""
+    cs = case(name)
+    if name in GPU_GRAPHS:
+        dm = domains(name)
+        return cs, dm.bc, dm.periods, dm.d
+    nl = cs.nl
+    seq = nl.block_is_seq.astype(bool)
+    bc = np.where(seq, np.arange(nl.num_blocks) % K, -1).astype(np.int32)
+    d = cs.delays["rand"]
+    cpd, _, _ = cs.sta.analyze(d)
+    periods = (np.asarray([0.55, 1.0, 1.6]) * F(cpd)).astype(F)
+    return cs, bc, periods, d
+
+
+# ------------------------------------------------------------------ replay
+
+def replay(nl, arch, tg, delay, bc, plan):
+    """pnr_sta_constrained in numpy float32. Returns arr[K, nb], req[R, nb],
+    slack, crit (clamped to 1 like the CPU engine), the worst period under
+    the CPU engine's first-met rule, and `top`: the achieved periods at the
+    largest achieved/constraint ratio."""
+    blocks, start = tg.level_arrays()
+    in_ptr, in_conn, out_ptr, out_conn, drv = tg.csr_arrays()
+    snk = nl.net_sinks
+    seq = nl.block_is_seq.astype(bool)
+    bd, t_out, t_in = _consts(nl, arch)
+    delay = np.ascontiguousarray(delay, F)
+    bc = np.asarray(bc)
+    nb, nc = nl.num_blocks, nl.num_conns
+    k_, r_ = plan.K, plan.R
+    L = len(start) - 1
+
+    arr = np.full((k_, nb), NEG, F)
+    for lv in range(L):
+        b = blocks[start[lv]:start[lv + 1]]
+        ff, comb = b[seq[b]], b[~seq[b]]
+        arr[:, ff] = np.where(bc[ff][None, :] == np.arange(k_)[:, None],
+                              t_out, NEG)
+        pos, own = _ragged(in_ptr, comb)
+        c = in_conn[pos]
+        for ci in range(k_):
+            v = arr[ci, drv[c]]
+            v = np.where(v > NEG, v + delay[c], v).astype(F)
+            m = np.full(len(comb), NEG, F)
+            np.maximum.at(m, own, v)
+            arr[ci, comb] = np.where(m > NEG, m + bd[comb], NEG)
+
+    req = np.full((r_, nb), POS, F)
+    req_ep = (plan.req_period - t_in).astype(F)
+    for lv in range(L - 1, -1, -1):
+        b = blocks[start[lv]:start[lv + 1]]
+        pos, own = _ragged(out_ptr, b)
+        c = out_conn[pos]
+        s = snk[c]
+        for row in range(r_):
+            r = req[row, s]
+            ri = np.where(seq[s],
+                          np.where(bc[s] == plan.req_domain[row],
+                                   req_ep[row], POS),
+                          np.where(r < POS, r - bd[s], POS)).astype(F)
+            ri = np.where(ri < POS, ri - delay[c], ri).astype(F)
+            m = np.full(len(b), POS, F)
+            np.minimum.at(m, own, ri)
+            req[row, b] = m
+
+    slack = np.full(nc, POS, F)
+    crit = np.zeros(nc, F)
+    worst_ratio, worst_period, top = F(0), plan.periods[0], set()
+    for pair in range(k_ * k_):
+        if plan.skip[pair]:
+            continue
+        ci, cj = divmod(pair, k_)
+        cons = plan.cons[pair]
+        a = arr[ci, drv]
+        r = req[plan.pair_row[pair], snk]
+        ri = np.where(seq[snk],
+                      np.where(bc[snk] == cj, cons - t_in, POS),
+                      np.where(r < POS, r - bd[snk], POS)).astype(F)
+        ok = np.nonzero((a > NEG) & (ri < POS))[0]
+        if not len(ok):
+            continue
+        s = (ri[ok] - (a[ok] + delay[ok])).astype(F)
+        slack[ok] = np.minimum(slack[ok], s)
+        cr = (F(1) - s / cons).astype(F)
+        crit[ok] = np.maximum(crit[ok], np.clip(cr, F(0), F(1)))
+        achieved = (cons - s).astype(F)
+        ratio = (achieved / cons).astype(F)
+        if ratio.max() > worst_ratio:
+            worst_ratio = ratio.max()
+            worst_period = achieved[np.argmax(ratio)]
+            top = set()
+        if ratio.max() == worst_ratio and worst_ratio > 0:
+            top |= set(achieved[ratio == worst_ratio].tolist())
+    slack[slack >= POS] = 0
+    assert arr.dtype == F and req.dtype == F and slack.dtype == F
+    return SimpleNamespace(arr=arr, req=req, slack=slack, crit=crit,
+                           wp=F(worst_period), top=top)
+
+
+@functools.lru_cache(maxsize=None)
+def expected(name, set_name):
+    """CPU engine and replay of one (graph, constraint set), computed
+    once."""
+    cs, bc, periods, d = setup_of(name)
+    skip, mult = constraint_set(set_name)
+    plan = constraint_plan(periods, skip, mult)
+    wp, slack, crit = cs.sta.analyze_domains(d, bc, periods, pair_skip=skip,
+                                             pair_mult=mult)
+    rp = replay(cs.nl, cs.arch, cs.sta.tg, d, bc, plan)
+    return SimpleNamespace(cs=cs, bc=bc, periods=periods, d=d, skip=skip,
+                           mult=mult, plan=plan, wp=F(wp), slack=slack,
+                           crit=crit, rp=rp)
+
+
+# ------------------------------------------------------- CPU: 1. the plan
+
+def test_plan_rows_and_tables():
+    per = domains("wide").periods
+    want = {"none": (3, [0, 1, 2] * 3),
+            "false01": (3, [0, 1, 2] * 3),
+            "false_row": (3, [0, 1, 2] * 3),
+            "all_false": (3, [0, 1, 2] * 3),
+            "mc01": (4, [0, 3, 2, 0, 1, 2, 0, 1, 2]),
+            "mc_shared": (5, [0, 3, 2, 0, 4, 2, 0, 3, 2]),
+            "false_and_mc": (4, [0, 3, 2, 0, 1, 2, 0, 1, 2])}
+    for name in SETS:
+        skip, mult = constraint_set(name)
+        p = constraint_plan(per, skip, mult)
+        rows, pair_row = want[name]
+        assert (p.K, p.R) == (3, rows), name
+        assert p.pair_row.tolist() == pair_row, name
+        for a, dt, n in ((p.cons, np.float32, 9), (p.pair_row, np.int32, 9),
+                         (p.skip, np.uint8, 9), (p.req_period, np.float32,
+                                                 rows),
+                         (p.req_domain, np.int32, rows)):
+            assert a.dtype == dt and a.shape == (n,), name
+        m = np.ones((3, 3), F) if mult is None else mult
+        prod = np.asarray([[F(per[cj]) * F(m[ci, cj]) for cj in range(3)]
+                           for ci in range(3)], F)
+        _same_bits(p.cons, prod.ravel(), f"{name} cons")
+        _same_bits(p.req_period[:3], per, f"{name} base rows")
+        assert p.req_domain[:3].tolist() == [0, 1, 2]
+        # every pair's row carries its constraint and its sink domain
+        _same_bits(p.req_period[p.pair_row], p.cons, f"{name} row periods")
+        assert p.req_domain[p.pair_row].tolist() == [0, 1, 2] * 3
+        s = np.zeros(9, np.uint8) if skip is None else skip.ravel()
+        assert np.array_equal(p.skip, s), name
+    # a product that is not exact in float32 is rounded once, in float32
+    p = constraint_plan([F(1e-9) / F(3)], None, [[F(1.1)]])
+    _same_bits(p.cons, [(F(1e-9) / F(3)) * F(1.1)], "rounded product")
+    assert p.R == 2 and p.pair_row.tolist() == [1]
+
+
+def test_plan_and_block_clock_errors():
+    per = [1e-9, 2e-9, 3e-9]
+    ok = np.ones((3, 3), F)
+    for bad in ([], np.ones(65) * 1e-9, [[1e-9]], [1e-9, 0.0], [1e-9, -1e-9],
+                [np.nan], [np.inf]):
+        with pytest.raises(ValueError):
+            constraint_plan(bad)
+    assert constraint_plan(np.ones(64) * 1e-9).K == 64
+    for bad in (np.ones((2, 3), F), np.ones(8, F), np.ones((3, 3, 1), F)):
+        with pytest.raises(ValueError):
+            constraint_plan(per, None, bad)
+        with pytest.raises(ValueError):
+            constraint_plan(per, bad.astype(np.uint8), None)
+    for v in (0.0, -2.0, np.nan, np.inf):
+        m = ok.copy()
+        m[1, 2] = v
+        with pytest.raises(ValueError):
+            constraint_plan(per, None, m)
+    bc = np.asarray([0, -1, 2, 1], np.int64)
+    out = check_block_clock(bc, 4, 3)
+    assert out.dtype == np.int32 and out.tolist() == [0, -1, 2, 1]
+    for bad, nb in ((bc, 5), (bc[:3], 4), (np.asarray([0, -2, 1, 1]), 4),
+                    (np.asarray([0, 3, 1, 1]), 4),
+                    (np.zeros((2, 2), np.int32), 4)):
+        with pytest.raises(ValueError):
+            check_block_clock(bad, nb, 3)
+    cs = case("chain")
+    with pytest.raises(ValueError):
+        ConstrainedSTA(cs.nl, cs.arch, [0, 1, -1], [1e-9, 2e-9])
+    with pytest.raises(ValueError):
+        ConstrainedSTA(cs.nl, cs.arch, [0, 2, -1, -1], [1e-9, 2e-9])
+    # a sequential block without a domain is legal
+    ConstrainedSTA(cs.nl, cs.arch, [0, -1, -1, -1], [1e-9, 2e-9])
+
+
+# ----------------------------------------------------- CPU: 2. the replay
+
+@pytest.mark.parametrize("name", CPU_GRAPHS)
+def test_replay_equals_cpu_engine(name):
+    for set_name in SETS:
+        e = expected(name, set_name)
+        tag = f"{name}/{set_name}"
+        _same_bits(e.rp.slack, e.slack, f"{tag} slack")
+        _same_bits(e.rp.crit, e.crit, f"{tag} crit")
+        _same_bits(e.rp.wp, e.wp, f"{tag} worst period")
+        if e.rp.top:
+            assert float(e.wp) in e.rp.top, tag
+        if set_name == "all_false":
+            assert e.wp == e.periods[0] and not e.rp.top
+            assert (e.slack == 0).all() and (e.crit == 0).all()
+        assert e.rp.arr.shape == (K, e.cs.nl.num_blocks)
+        assert e.rp.req.shape == (e.plan.R, e.cs.nl.num_blocks)
+    # the sets change the answer (the comparison above is not vacuous)
+    if name in GPU_GRAPHS:
+        base = expected(name, "none")
+        for set_name in ("false01", "false_row", "mc01", "mc_shared"):
+            e = expected(name, set_name)
+            assert (_bits32(e.crit) != _bits32(base.crit)).any(), set_name
+
+
+def _bits32(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def _domain_top(sta, d, bc, plan):
+    """test_sta_exact.domains()'s rebuild with `cons` in place of
+    periods[cj]: one CPU run per unskipped pair."""
+    k = plan.K
+    best, top = F(-1), set()
+    mult = plan.mult.reshape(k, k)
+    for pair in np.nonzero(plan.skip == 0)[0]:
+        skip = np.ones((k, k), np.uint8)
+        skip.ravel()[pair] = 0
+        _, s, cr = sta.analyze_domains(d, bc, plan.periods, pair_skip=skip,
+                                       pair_mult=mult)
+        reached = ~((s == 0) & (cr == 0))
+        if not reached.any():
+            continue
+        achieved = plan.cons[pair] - s[reached]
+        ratio = achieved / plan.cons[pair]
+        assert ratio.dtype == F
+        if ratio.max() > best:
+            best, top = ratio.max(), set()
+        if ratio.max() == best:
+            top |= set(achieved[ratio == best].tolist())
+    return top
+
+
+@pytest.mark.parametrize("name", GPU_GRAPHS)
+def test_replay_top_is_cpu_rebuilt_top(name):
+    """The replay's `top`, which the GPU tests hold the device's worst
+    period to, is the set rebuilt from the CPU engine alone: one run per
+    unskipped pair, as test_sta_exact.domains() does, with `cons` in place
+    of periods[cj]. Without constraints it is domains()'s own set."""
+    e = expected(name, "none")
+    assert e.rp.top == domains(name).top | {float(e.wp)}
+    for set_name in SETS:
+        e = expected(name, set_name)
+        top = _domain_top(e.cs.sta, e.d, e.bc, e.plan)
+        assert top == e.rp.top, set_name
+        if set_name == "all_false":
+            assert not top
+        # (stride has one source flip-flop, in domain 0: a false source
+        # row leaves it without an analysable pair as well)
+        assert top or set_name in ("all_false", "false_row")
+
+
+# ---------------------------------------------- CPU: 3. the CPU loop engine
+
+@pytest.mark.parametrize("name", ("wide_het", "chain", "idle_ff"))
+def test_constrained_sta_equals_analyze_domains(name):
+    for set_name in SETS:
+        e = expected(name, set_name)
+        eng = ConstrainedSTA(e.cs.nl, e.cs.arch, e.bc, e.periods, e.skip,
+                             e.mult)
+        assert eng.num_conns == e.cs.nl.num_conns
+        assert eng.netlist is e.cs.nl and not hasattr(eng, "analyze_device")
+        wp, slack, crit = eng.analyze(e.d)
+        _same_bits(F(wp), e.wp, f"{name}/{set_name} period")
+        _same_bits(slack, e.slack, f"{name}/{set_name} slack")
+        _same_bits(crit, e.crit, f"{name}/{set_name} crit")
+
+
+def two_ff():
+    """Flip-flop 0 (domain 0) -> combinational block 2 -> flip-flop 1
+    (domain 1): both connections are reached through pair (0, 1) only."""
+    nl = NetlistPy([0, 0, 1], [1, 1, 0], [0, 2], [0, 1, 2], [2, 1])
+    return nl, np.asarray([0, 1, -1], np.int32)
+
+
+def test_false_pair_zeroes_its_connections():
+    from parallel_eda_amd.arch.archdef import get_arch
+    nl, bc = two_ff()
+    arch = get_arch("tiny")
+    d = np.asarray([0.4e-9, 0.7e-9], F)
+    per = [2e-9, 3e-9]
+    skip = np.zeros((2, 2), np.uint8)
+    skip[0, 1] = 1
+    _, _, crit = STA(nl, arch).analyze(d)
+    assert (crit > 0).all()
+    _, slack, crit = ConstrainedSTA(nl, arch, bc, per).analyze(d)
+    assert (crit > 0).all() and (slack != 0).all()
+    wp, slack, crit = ConstrainedSTA(nl, arch, bc, per, skip).analyze(d)
+    assert (slack == 0).all() and (_bits32(crit) == 0).all()
+    assert F(wp) == F(per[0])
+    # the other three pairs false instead: nothing changes for (0, 1)
+    wp2, slack2, crit2 = ConstrainedSTA(nl, arch, bc, per,
+                                        1 - skip).analyze(d)
+    assert (crit2 > 0).all()
+    # multicycle 2 on the pair: one more period of slack, to rounding
+    mult = np.ones((2, 2), F)
+    mult[0, 1] = 2
+    _, slack3, _ = ConstrainedSTA(nl, arch, bc, per, None, mult).analyze(d)
+    assert np.allclose(slack3 - slack2, per[1], rtol=1e-5)
+
+
+# ------------------------------------------------------------ GPU: 6. exact
+
+def _gsta(cs, max_crit):
+    from parallel_eda_amd.timing.gpu_sta import GpuSTA
+    return GpuSTA(cs.nl, cs.arch, max_crit=max_crit)
+
+
+def _engine(gs, e):
+    from parallel_eda_amd.timing.gpu_sta import GpuConstrainedSTA
+    return GpuConstrainedSTA(gs, e.bc, e.periods, e.skip, e.mult)
+
+
+def _check(eng, e, got, tag):
+    wp, slack, crit = got
+    cap = F(eng.max_crit)
+    _same_bits(slack, e.slack, f"{tag} slack")
+    _same_bits(crit, np.minimum(e.crit, cap), f"{tag} crit")
+    _same_bits(eng.arr_rows(), e.rp.arr, f"{tag} arr rows")
+    _same_bits(eng.req_rows(), e.rp.req, f"{tag} req rows")
+    if e.rp.top:
+        assert float(F(wp)) in e.rp.top, (tag, wp, sorted(e.rp.top)[:4])
+        assert F(wp) == F(max(e.rp.top)), tag      # larger period on a tie
+    else:
+        assert F(wp) == e.periods[0], tag
+
+
+@gpu
+@pytest.mark.parametrize("name", GPU_GRAPHS)
+def test_gpu_constrained_exact(name):
+    cs = case(name)
+    if name == "stride":
+        assert cs.nl.num_conns > ONE_PASS
+    if name == "wide":
+        _, start = cs.sta.tg.level_arrays()
+        assert {255, 256, 257} <= set(np.diff(start).tolist())
+    for max_crit in (1.0, 0.99):
+        gs = _gsta(cs, max_crit)
+        for set_name in SETS:
+            e = expected(name, set_name)
+            eng = _engine(gs, e)
+            assert (eng.K, eng.R) == (e.plan.K, e.plan.R)
+            tag = f"{name}/{set_name}/max_crit={max_crit}"
+            got = eng.analyze(e.d)
+            _check(eng, e, got, tag)
+            if set_name == "all_false":
+                assert F(got[0]) == e.periods[0]
+                assert (_bits32(got[1]) == 0).all()
+                assert (_bits32(got[2]) == 0).all()
+
+
+# ------------------------------------------------------- GPU: 7. edge cases
+
+@gpu
+def test_gpu_k1_and_k64():
+    from parallel_eda_amd.timing.gpu_sta import GpuConstrainedSTA
+    # K = 1 on a real graph, with and without a self multicycle
+    cs = case("wide")
+    d = cs.delays["rand"]
+    seq = cs.nl.block_is_seq.astype(bool)
+    one = np.where(seq, 0, -1).astype(np.int32)
+    cpd, _, _ = cs.sta.analyze(d)
+    gs = _gsta(cs, 1.0)
+    for mult in (None, np.asarray([[2.0]], F)):
+        plan = constraint_plan([cpd], None, mult)
+        assert plan.R == (1 if mult is None else 2)
+        wp_c, sl_c, cr_c = cs.sta.analyze_domains(d, one, [cpd],
+                                                  pair_mult=mult)
+        rp = replay(cs.nl, cs.arch, cs.sta.tg, d, one, plan)
+        eng = GpuConstrainedSTA(gs, one, [cpd], None, mult)
+        wp, slack, crit = eng.analyze(d)
+        _same_bits(slack, sl_c, f"K=1 mult={mult} slack")
+        _same_bits(crit, cr_c, f"K=1 mult={mult} crit")
+        _same_bits(eng.arr_rows(), rp.arr, "K=1 arr")
+        _same_bits(eng.req_rows(), rp.req, "K=1 req")
+        assert float(F(wp)) in rp.top
+    # K = 64 on the four-block chain: 4,096 pairs per connection and 128
+    # backward rows (besides its single-cycle row every sink domain has one
+    # multicycle row, multiplier 2 for the even and 3 for the odd domains,
+    # read by every other source domain)
+    cs = case("chain")
+    k = 64
+    d = np.asarray([0.3e-9, 0.5e-9, 0.9e-9], F)
+    per = ((1.0 + np.arange(k) / 16.0) * 1e-9).astype(F)
+    mult = np.ones((k, k), F)
+    ci, cj = np.indices((k, k))
+    mult[(ci + cj) % 2 == 1] = 2
+    mult[:, 1::2][mult[:, 1::2] == 2] = 3
+    mult[np.arange(k), np.arange(k)] = 1
+    skip = ((ci * 7 + cj * 3) % 11 == 0).astype(np.uint8)
+    plan = constraint_plan(per, skip, mult)
+    assert plan.R == 128
+    gs = _gsta(cs, 1.0)
+    for f0, f1 in ((0, 1), (63, 62), (62, 63), (5, 40)):
+        bc = np.asarray([f0, f1, -1, -1], np.int32)
+        skip[f0, f1] = 0
+        plan = constraint_plan(per, skip, mult)
+        wp_c, sl_c, cr_c = cs.sta.analyze_domains(d, bc, per, pair_skip=skip,
+                                                  pair_mult=mult)
+        rp = replay(cs.nl, cs.arch, cs.sta.tg, d, bc, plan)
+        _same_bits(rp.slack, sl_c, "K=64 replay slack")
+        eng = GpuConstrainedSTA(gs, bc, per, skip, mult)
+        wp, slack, crit = eng.analyze(d)
+        assert (sl_c != 0).any()
+        _same_bits(slack, sl_c, f"K=64 {f0}->{f1} slack")
+        _same_bits(crit, cr_c, f"K=64 {f0}->{f1} crit")
+        _same_bits(eng.arr_rows(), rp.arr, "K=64 arr")
+        _same_bits(eng.req_rows(), rp.req, "K=64 req")
+        assert float(F(wp)) in rp.top
+    with pytest.raises(ValueError):
+        GpuConstrainedSTA(gs, bc, np.ones(65, F) * 1e-9)
+    with pytest.raises(ValueError):
+        GpuConstrainedSTA(gs, [0, 64, -1, -1], per)
+    with pytest.raises(ValueError):
+        gs.analyze_domains(d, bc, np.ones(65, F) * 1e-9,
+                           pair_skip=np.zeros((65, 65), np.uint8))
+
+
+# ------------------------------------------------------------ GPU: 8. reuse
+
+@gpu
+def test_gpu_engine_reuse_no_allocation():
+    import torch
+    name = "wide_het"
+    e = expected(name, "mc_shared")
+    cs = e.cs
+    gs = _gsta(cs, 1.0)
+    eng = _engine(gs, e)
+    d2 = cs.delays["outlier"]
+    wp2, sl2, cr2 = cs.sta.analyze_domains(d2, e.bc, e.periods,
+                                           pair_skip=e.skip, pair_mult=e.mult)
+    rp2 = replay(cs.nl, cs.arch, cs.sta.tg, d2, e.bc, e.plan)
+    e2 = SimpleNamespace(slack=sl2, crit=cr2, rp=rp2, periods=e.periods)
+
+    def poison():
+        for t in eng.owned_buffers():
+            if t.dtype == torch.float32:
+                t.fill_(float("nan"))
+            else:
+                t.fill_(-1)                     # 0xFF in every byte
+
+    assert len(eng.owned_buffers()) == 6
+    _check(eng, e, eng.analyze(e.d), "first call")
+    poison()
+    _check(eng, e2, eng.analyze(d2), "other delays after poison")
+    poison()
+    _check(eng, e, eng.analyze(e.d), "first delays again after poison")
+    for t in eng.owned_buffers()[:4]:
+        assert not bool(t.isnan().any())
+    # the shared single-clock engine is untouched by all of this
+    cpd, slack, _ = gs.analyze(e.d)
+    cpd_c, slack_c, _ = cs.sta.analyze(e.d)
+    _same_bits(F(cpd), F(cpd_c), "single-clock cpd after constrained calls")
+    _same_bits(slack, slack_c, "single-clock slack after constrained calls")
+    # analyze_device: same tensors back, no allocation
+    t1 = torch.from_numpy(e.d).to("cuda:0")
+    t2 = torch.from_numpy(d2).to("cuda:0")
+    out = eng.analyze_device(t1)
+    torch.cuda.synchronize()
+    assert out[0] is eng.t_period and out[1] is eng.t_slack \
+        and out[2] is eng.t_crit
+    assert out[0].dtype == torch.float32 and out[0].numel() == 1
+    for t in (t2, t1):
+        before = torch.cuda.memory_allocated()
+        out = eng.analyze_device(t)
+        assert torch.cuda.memory_allocated() == before
+        torch.cuda.synchronize()
+        assert torch.cuda.memory_allocated() == before
+    _same_bits(out[1].cpu().numpy(), e.slack, "slack of the third call")
+    _same_bits(out[2].cpu().numpy(), e.crit, "crit of the third call")
+    assert float(out[0].item()) in e.rp.top
+    with pytest.raises(ValueError):
+        eng.analyze_device(t1[:-1])
+    with pytest.raises(ValueError):
+        eng.analyze_device(t1.double())
+
+
+# ------------------------------------- GPU: 9. GpuSTA.analyze_domains(pairs)
+
+@gpu
+@pytest.mark.parametrize("name", ("wide_het", "mid"))
+def test_gpu_analyze_domains_pair_arguments(name):
+    cs, dm = case(name), domains(name)
+    gs = _gsta(cs, 1.0)
+    # both None: today's entry point, today's result
+    wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
+    _same_bits(slack, dm.slack, "old entry slack")
+    _same_bits(crit, dm.crit, "old entry crit")
+    _same_bits(F(wp), F(dm.wp), "old entry period")
+    for set_name in ("false01", "mc_shared", "false_and_mc", "all_false"):
+        e = expected(name, set_name)
+        wp, slack, crit = gs.analyze_domains(e.d, e.bc, e.periods,
+                                             pair_skip=e.skip,
+                                             pair_mult=e.mult)
+        _same_bits(slack, e.slack, f"{set_name} slack")
+        _same_bits(crit, e.crit, f"{set_name} crit")
+        if e.rp.top:
+            assert float(F(wp)) in e.rp.top
+        else:
+            assert F(wp) == e.periods[0]
+    # the two device implementations agree without constraints
+    e = expected(name, "none")
+    ones = np.ones((K, K), F)
+    wp_n, slack_n, crit_n = gs.analyze_domains(dm.d, dm.bc, dm.periods,
+                                               pair_mult=ones)
+    _same_bits(slack_n, dm.slack, "new entry, no constraint: slack")
+    _same_bits(crit_n, dm.crit, "new entry, no constraint: crit")
+    _same_bits(F(wp_n), F(dm.wp), "new entry, no constraint: period")
