@@ -318,7 +318,9 @@ PYBIND11_MODULE(_pnr_cpu, m) {
                                  py::array_t<float, py::array::c_style | py::array::forcecast> conn_delay,
                                  py::array_t<int32_t, py::array::c_style | py::array::forcecast> block_clock,
                                  py::array_t<float, py::array::c_style | py::array::forcecast> periods,
-                                 py::object pair_skip, py::object pair_mult) {
+                                 py::object pair_skip, py::object pair_mult,
+                                 py::object launch, py::object capture,
+                                 bool pair_slack) {
         py::ssize_t n = conn_delay.size();
         py::array_t<float> slack(n), crit(n);
         const uint8_t* ps = nullptr;
@@ -338,13 +340,38 @@ PYBIND11_MODULE(_pnr_cpu, m) {
             throw std::runtime_error("pair_mult must be KxK");
           pm = pma.data();
         }
+        // per-block tables: SDC I/O delays folded into launch / capture
+        py::array_t<float, py::array::c_style | py::array::forcecast> la, ca;
+        const float* lp = nullptr;
+        const float* cp = nullptr;
+        if ((py::ssize_t)block_clock.size() != (py::ssize_t)t.nl_->num_blocks)
+          throw std::runtime_error("block_clock must have num_blocks entries");
+        if (!launch.is_none()) {
+          la = launch.cast<decltype(la)>();
+          if ((py::ssize_t)la.size() != (py::ssize_t)t.nl_->num_blocks)
+            throw std::runtime_error("launch must have num_blocks entries");
+          lp = la.data();
+        }
+        if (!capture.is_none()) {
+          ca = capture.cast<decltype(ca)>();
+          if ((py::ssize_t)ca.size() != (py::ssize_t)t.nl_->num_blocks)
+            throw std::runtime_error("capture must have num_blocks entries");
+          cp = ca.data();
+        }
+        py::array_t<float> pslack(pair_slack ? (py::ssize_t)K * K : 0);
         float wp = t.analyze_domains(conn_delay.data(), block_clock.data(),
                                      periods.data(), K,
                                      slack.mutable_data(),
-                                     crit.mutable_data(), ps, pm);
-        return py::make_tuple(wp, slack, crit);
+                                     crit.mutable_data(), ps, pm, lp, cp,
+                                     pair_slack ? pslack.mutable_data()
+                                                : nullptr);
+        if (pair_slack)
+          return py::tuple(py::make_tuple(wp, slack, crit, pslack));
+        return py::tuple(py::make_tuple(wp, slack, crit));
       }, py::arg("conn_delay"), py::arg("block_clock"), py::arg("periods"),
-         py::arg("pair_skip") = py::none(), py::arg("pair_mult") = py::none())
+         py::arg("pair_skip") = py::none(), py::arg("pair_mult") = py::none(),
+         py::arg("launch") = py::none(), py::arg("capture") = py::none(),
+         py::arg("pair_slack") = false)
       .def("level_arrays", [](TimingGraph& t) {
         std::vector<int32_t> blocks, start;
         t.level_arrays(blocks, start);

@@ -12,6 +12,7 @@
 // (csrc/hip/sta_kernel.hip), which run the same sweeps level-synchronously.
 #include "pnr.h"
 #include <algorithm>
+#include <limits>
 #include <map>
 
 namespace pnr {
@@ -98,14 +99,26 @@ class TimingGraph {
   // analyzed; a multiplied pair's setup constraint is periods[cj]*mult
   // (the backward pass is re-run per distinct (cj, mult) so comb
   // fan-in cones see the adjusted requirement exactly).
+  // launch / capture: optional per-block tables (SDC set_input_delay /
+  // set_output_delay on pads, read_sdc.c): a sequential block launches at
+  // launch[b] instead of T_seq_out and an endpoint requires
+  // constraint - capture[snk] instead of constraint - T_seq_in.
+  // pair_slack: optional output [K*K], the least slack per (src, sink)
+  // pair; +inf for a skipped pair or one with no analysed connection.
   float analyze_domains(const float* conn_delay, const int32_t* block_clock,
                         const float* periods, int K,
                         float* slack, float* crit,
                         const uint8_t* pair_skip = nullptr,
-                        const float* pair_mult = nullptr) {
+                        const float* pair_mult = nullptr,
+                        const float* launch = nullptr,
+                        const float* capture = nullptr,
+                        float* pair_slack = nullptr) {
     int nb = nl_->num_blocks;
     int64_t nconn = (int64_t)nl_->net_sinks.size();
     const float NEG = -3.0e38f, POS = 3.0e38f;
+    if (pair_slack)
+      for (int p = 0; p < K * K; ++p)
+        pair_slack[p] = std::numeric_limits<float>::infinity();
     std::vector<std::vector<float>> arr(K), req(K);
     // forward per source domain
     for (int ci = 0; ci < K; ++ci) {
@@ -113,7 +126,8 @@ class TimingGraph {
       a.assign(nb, NEG);
       for (int b : topo_) {
         if (nl_->block_is_seq[b]) {
-          a[b] = (block_clock[b] == ci) ? T_seq_out_ : NEG;
+          a[b] = (block_clock[b] == ci) ? (launch ? launch[b] : T_seq_out_)
+                                        : NEG;
           continue;
         }
         float m = NEG;
@@ -129,7 +143,6 @@ class TimingGraph {
     // backward per (sink domain, constraint period)
     auto backward = [&](int cj, float period, std::vector<float>& r) {
       r.assign(nb, POS);
-      float req_ep = period - T_seq_in_;
       for (auto it = topo_.rbegin(); it != topo_.rend(); ++it) {
         int b = *it;
         float m = POS;
@@ -138,7 +151,8 @@ class TimingGraph {
           int snk = nl_->net_sinks[c];
           float ri;
           if (nl_->block_is_seq[snk])
-            ri = (block_clock[snk] == cj) ? req_ep : POS;
+            ri = (block_clock[snk] == cj)
+                     ? period - (capture ? capture[snk] : T_seq_in_) : POS;
           else
             ri = (r[snk] < POS) ? r[snk] - blk_delay_[snk] : POS;
           if (ri < POS) ri -= conn_delay[c];
@@ -173,12 +187,16 @@ class TimingGraph {
           if (arr[ci][drv] <= NEG) continue;
           float ri;
           if (nl_->block_is_seq[snk])
-            ri = (block_clock[snk] == cj) ? constraint - T_seq_in_ : POS;
+            ri = (block_clock[snk] == cj)
+                     ? constraint - (capture ? capture[snk] : T_seq_in_)
+                     : POS;
           else
             ri = (R[snk] < POS) ? R[snk] - blk_delay_[snk] : POS;
           if (ri >= POS) continue;
           float s = ri - (arr[ci][drv] + conn_delay[c]);
           if (s < slack[c]) slack[c] = s;
+          if (pair_slack && s < pair_slack[ci * K + cj])
+            pair_slack[ci * K + cj] = s;
           float cr = 1.0f - s / constraint;
           if (cr > crit[c]) crit[c] = cr < 0 ? 0.0f : (cr > 1 ? 1.0f : cr);
           float achieved = constraint - s;

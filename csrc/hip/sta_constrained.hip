@@ -17,7 +17,15 @@
 //
 // Every constraint comes from host tables (timing/constraints.py): the device
 // never multiplies a period by a multiplier, so there is no product for the
-// compiler to contract into the subtraction that follows it.
+// compiler to contract into the subtraction that follows it. The same holds
+// for the per-block launch / capture tables (SDC I/O delays on pads): clock
+// to Q plus input delay and setup plus output delay are summed on the host;
+// a null table means the scalar, and then every bit is what it was without
+// the tables.
+//
+// stc_pair_slack (pnr_sta_pair_slack) is the report side: the least slack per
+// (source, sink) pair from the arr / req rows of the last analysis, on
+// demand, outside the loops.
 #include "pnr_hip.h"
 
 namespace pnrh {
@@ -43,6 +51,8 @@ struct StcDev {
   const int32_t* req_domain;     // [R]
   float* arr;                    // [num_blocks * K]
   float* req;                    // [num_blocks * R]
+  const float* launch;           // per block; nullptr => T_seq_out
+  const float* capture;          // per block; nullptr => T_seq_in
 };
 
 #define STC_NEG (-3.0e38f)
@@ -58,7 +68,8 @@ __global__ void stc_fwd_level(StcDev s, const float* __restrict__ delay,
   int32_t b = s.level_blocks[lv0 + i];
   float* out = s.arr + (int64_t)b * s.K + ci;
   if (s.is_seq[b]) {
-    *out = (s.block_clock[b] == ci) ? s.T_seq_out : STC_NEG;
+    float t0 = s.launch ? s.launch[b] : s.T_seq_out;
+    *out = (s.block_clock[b] == ci) ? t0 : STC_NEG;
     return;
   }
   float m = STC_NEG;
@@ -81,14 +92,18 @@ __global__ void stc_bwd_level(StcDev s, const float* __restrict__ delay,
   int32_t row = (int32_t)(t - (int64_t)i * s.R);
   int32_t b = s.level_blocks[lv0 + i];
   int32_t cj = s.req_domain[row];
-  float req_ep = s.req_period[row] - s.T_seq_in;
+  float period = s.req_period[row];
   float m = STC_POS;
   for (int64_t k = s.out_ptr[b]; k < s.out_ptr[b + 1]; ++k) {
     int64_t c = s.out_conn[k];
     int32_t snk = s.conn_sink[c];
     float ri;
     if (s.is_seq[snk]) {
-      ri = (s.block_clock[snk] == cj) ? req_ep : STC_POS;
+      // a select, not a branch: the block that drives many flip-flops
+      // walks them in one thread, and a branch here costs 5 % (null table)
+      // to 19 % (table) of that walk (docs/MEASUREMENTS.md)
+      float cap = s.capture ? s.capture[snk] : s.T_seq_in;
+      ri = (s.block_clock[snk] == cj) ? period - cap : STC_POS;
     } else {
       float td = s.blk_delay ? s.blk_delay[snk] : s.T_clb;
       float r = s.req[(int64_t)snk * s.R + row];
@@ -98,6 +113,37 @@ __global__ void stc_bwd_level(StcDev s, const float* __restrict__ delay,
     m = fminf(m, ri);
   }
   s.req[(int64_t)b * s.R + row] = m;
+}
+
+// slack of connection c under pair (ci, cj) = pair; false when the pair is
+// false or does not reach the connection
+__device__ __forceinline__ bool stc_conn_pair_slack(
+    const StcDev& s, const float* __restrict__ delay, int64_t c, int32_t pair,
+    float constraint, float* sl) {
+  if (s.skip[pair]) return false;             // false path
+  int32_t ci = pair / s.K, cj = pair - ci * s.K;
+  int32_t drv = s.conn_driver[c];
+  int32_t snk = s.conn_sink[c];
+  float a = s.arr[(int64_t)drv * s.K + ci];
+  if (a <= STC_NEG) return false;
+  float ri;
+  if (s.is_seq[snk]) {
+    float cap = s.capture ? s.capture[snk] : s.T_seq_in;
+    ri = (s.block_clock[snk] == cj) ? constraint - cap : STC_POS;
+  } else {
+    float td = s.blk_delay ? s.blk_delay[snk] : s.T_clb;
+    float r = s.req[(int64_t)snk * s.R + s.pair_row[pair]];
+    ri = (r < STC_POS) ? r - td : STC_POS;
+  }
+  if (ri >= STC_POS) return false;
+  *sl = ri - (a + delay[c]);
+  return true;
+}
+
+// order-preserving bits of a float: unsigned order = float order
+__device__ __forceinline__ unsigned stc_order_bits(float v) {
+  unsigned b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
 // one thread per (conn, ci, cj): worst slack / max criticality per conn and
@@ -111,27 +157,11 @@ __global__ void stc_pairs(StcDev s, const float* __restrict__ delay,
   for (; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
     int64_t c = idx / KK;
     int32_t pair = (int32_t)(idx - c * KK);
-    if (s.skip[pair]) continue;               // false path
-    int32_t ci = pair / s.K, cj = pair - ci * s.K;
-    int32_t drv = s.conn_driver[c];
-    int32_t snk = s.conn_sink[c];
-    float a = s.arr[(int64_t)drv * s.K + ci];
-    if (a <= STC_NEG) continue;
     float constraint = s.cons[pair];
-    float ri;
-    if (s.is_seq[snk]) {
-      ri = (s.block_clock[snk] == cj) ? constraint - s.T_seq_in : STC_POS;
-    } else {
-      float td = s.blk_delay ? s.blk_delay[snk] : s.T_clb;
-      float r = s.req[(int64_t)snk * s.R + s.pair_row[pair]];
-      ri = (r < STC_POS) ? r - td : STC_POS;
-    }
-    if (ri >= STC_POS) continue;
-    float sl = ri - (a + delay[c]);
+    float sl;
+    if (!stc_conn_pair_slack(s, delay, c, pair, constraint, &sl)) continue;
     // min slack per conn: atomicMin on order-preserving bits
-    unsigned sb = __float_as_uint(sl);
-    sb = (sb & 0x80000000u) ? ~sb : (sb | 0x80000000u);
-    atomicMin((unsigned*)&slack[c], sb);
+    atomicMin((unsigned*)&slack[c], stc_order_bits(sl));
     float cr = 1.0f - sl / constraint;
     cr = fminf(fmaxf(cr, 0.0f), s.max_crit);
     atomicMax((unsigned*)&crit[c], __float_as_uint(cr));  // cr >= 0
@@ -163,6 +193,46 @@ __global__ void stc_finish(int64_t num_conns, float* slack,
   }
 }
 
+// least slack per pair over all connections, as order-preserving bits in
+// out[K*K] (preset to all-ones). One thread per (conn, pair) with the pair
+// fastest, so a wave's lanes spread over the words of the table: each
+// workgroup takes its minima in an LDS table of K*K words (16 KB at K = 64)
+// and then issues one global atomicMin per word it touched, instead of
+// num_conns * K * K global atomics onto K * K words.
+__global__ void stc_pair_slack(StcDev s, const float* __restrict__ delay,
+                               unsigned* out) {
+  extern __shared__ unsigned stc_tab[];
+  const int32_t KK = s.K * s.K;
+  for (int32_t p = threadIdx.x; p < KK; p += blockDim.x)
+    stc_tab[p] = 0xFFFFFFFFu;
+  __syncthreads();
+  const int64_t total = s.num_conns * (int64_t)KK;
+  int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
+    int64_t c = idx / KK;
+    int32_t pair = (int32_t)(idx - c * KK);
+    float sl;
+    if (!stc_conn_pair_slack(s, delay, c, pair, s.cons[pair], &sl)) continue;
+    atomicMin(&stc_tab[pair], stc_order_bits(sl));
+  }
+  __syncthreads();
+  for (int32_t p = threadIdx.x; p < KK; p += blockDim.x) {
+    unsigned v = stc_tab[p];
+    if (v != 0xFFFFFFFFu) atomicMin(&out[p], v);
+  }
+}
+
+// decode the pair table; all-ones (no analysed connection) => +inf
+__global__ void stc_pair_slack_finish(int32_t KK, const unsigned* bits,
+                                      float* out) {
+  int32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= KK) return;
+  unsigned sb = bits[p];
+  if (sb == 0xFFFFFFFFu) { out[p] = __uint_as_float(0x7F800000u); return; }
+  sb = (sb & 0x80000000u) ? (sb & 0x7FFFFFFFu) : ~sb;
+  out[p] = __uint_as_float(sb);
+}
+
 }  // namespace pnrh
 
 using namespace pnrh;
@@ -187,17 +257,27 @@ struct StaConstrainedArgs {
   unsigned long long* worst_bits;   // [1]
   float* period_out;                // [1]
   const int32_t* level_start_host;  // host copy for launch bounds
+  const float* launch;              // [num_blocks]; nullptr => T_seq_out
+  const float* capture;             // [num_blocks]; nullptr => T_seq_in
 };
 
+static bool stc_args_ok(const StaConstrainedArgs* a) {
+  return !(a->K < 1 || a->K > 64 || a->R < a->K || a->R > 2 * 64 * 64 ||
+           a->num_blocks < 0 || a->num_conns < 0 || a->num_levels < 0);
+}
+
+static StcDev stc_dev(const StaConstrainedArgs* a) {
+  return StcDev{a->level_blocks, a->in_ptr, a->in_conn, a->out_ptr,
+                a->out_conn, a->conn_driver, a->conn_sink, a->is_seq,
+                a->blk_delay, a->block_clock, a->T_clb, a->T_seq_out,
+                a->T_seq_in, a->max_crit, a->num_blocks, a->K, a->R,
+                a->num_conns, a->cons, a->pair_row, a->skip, a->req_period,
+                a->req_domain, a->arr, a->req, a->launch, a->capture};
+}
+
 int pnr_sta_constrained(const StaConstrainedArgs* a, void* stream) {
-  if (a->K < 1 || a->K > 64 || a->R < a->K || a->R > 2 * 64 * 64 ||
-      a->num_blocks < 0 || a->num_conns < 0 || a->num_levels < 0)
-    return (int)hipErrorInvalidValue;
-  StcDev s{a->level_blocks, a->in_ptr, a->in_conn, a->out_ptr, a->out_conn,
-           a->conn_driver, a->conn_sink, a->is_seq, a->blk_delay,
-           a->block_clock, a->T_clb, a->T_seq_out, a->T_seq_in, a->max_crit,
-           a->num_blocks, a->K, a->R, a->num_conns, a->cons, a->pair_row,
-           a->skip, a->req_period, a->req_domain, a->arr, a->req};
+  if (!stc_args_ok(a)) return (int)hipErrorInvalidValue;
+  StcDev s = stc_dev(a);
   hipStream_t st = (hipStream_t)stream;
   const int32_t* ls = a->level_start_host;
   // the level table must partition [0, num_blocks): it bounds every launch
@@ -236,6 +316,29 @@ int pnr_sta_constrained(const StaConstrainedArgs* a, void* stream) {
   if (cgrid < 1) cgrid = 1;  // the period is decoded even without connections
   hipLaunchKernelGGL(stc_finish, dim3(cgrid), dim3(256), 0, st, a->num_conns,
                      a->slack, a->worst_bits, a->req_period, a->period_out);
+  return (int)hipGetLastError();
+}
+
+// Least slack per (source, sink) pair of the analysis whose arr / req rows
+// are in place: a->delay must be the delay vector of that analysis. bits is
+// scratch [K*K], out float32 [K*K] (+inf where no connection is analysed).
+int pnr_sta_pair_slack(const StaConstrainedArgs* a, unsigned* bits, float* out,
+                       void* stream) {
+  if (!stc_args_ok(a) || !a->delay || !bits || !out)
+    return (int)hipErrorInvalidValue;
+  StcDev s = stc_dev(a);
+  hipStream_t st = (hipStream_t)stream;
+  const int KK = a->K * a->K;
+  hipError_t me = hipMemsetAsync(bits, 0xFF, KK * sizeof(unsigned), st);
+  if (me != hipSuccess) return (int)me;
+  int64_t total = a->num_conns * (int64_t)KK;
+  int64_t g64 = (total + 255) / 256;
+  int grid = (int)(g64 < 1024 ? g64 : 1024);
+  if (grid > 0)
+    hipLaunchKernelGGL(stc_pair_slack, dim3(grid), dim3(256),
+                       KK * sizeof(unsigned), st, s, a->delay, bits);
+  hipLaunchKernelGGL(stc_pair_slack_finish, dim3((KK + 255) / 256), dim3(256),
+                     0, st, KK, bits, out);
   return (int)hipGetLastError();
 }
 

@@ -80,6 +80,13 @@ def build_parser():
                         "domains). Each router iteration's cpd in the log "
                         "and the stats history is then the worst achieved "
                         "period; the final reports keep the CPU engine")
+    p.add_argument("--sdc_report", type=str, default=None,
+                   help="after routing, write one line per analysed "
+                        "(source, sink) clock pair of the --sdc constraints: "
+                        "source clock, sink clock, constraint and worst "
+                        "slack in ns. With --sdc_driven the table is the "
+                        "loop engine's own (computed on the GPU with "
+                        "--sta_engine gpu), otherwise the CPU engine's")
     p.add_argument("--draw_place", type=str, default=None,
                    help="render the placement to SVG (headless draw.c)")
     p.add_argument("--draw_route", type=str, default=None,
@@ -147,6 +154,10 @@ def main(argv=None):
         parser.error("--sdc_driven requires --sdc")
     if args.sdc_driven and args.router_algorithm != "timing_driven":
         parser.error("--sdc_driven requires --router_algorithm timing_driven")
+    if args.sdc_report and not args.sdc:
+        parser.error("--sdc_report requires --sdc")
+    if args.sdc_report and args.router_algorithm != "timing_driven":
+        parser.error("--sdc_report requires --router_algorithm timing_driven")
     from .arch.archdef import get_arch
     from .arch.xml_parser import parse_arch_xml, size_grid_for_netlist
     from .io.synth import synth_netlist, spec_for_arch
@@ -214,6 +225,12 @@ def main(argv=None):
             print(f"SDC: false path {f_ or '*'} -> {t_ or '*'}")
         for (f_, t_, n_) in sdc_all["multicycle"]:
             print(f"SDC: multicycle {n_} {f_ or '*'} -> {t_ or '*'}")
+        for (k_, c_, v_, pat_) in sdc_all["io_delays"]:
+            print(f"SDC: {k_} delay {v_*1e9:.3f} ns, clock '{c_}', ports "
+                  f"{' '.join(pat_) if pat_ is not None else '*'}")
+        for grp_ in sdc_all["clock_groups"]:
+            print("SDC: exclusive clock groups "
+                  + " | ".join(" ".join(g_) for g_ in grp_))
     if args.sdc_driven:
         from .timing.constraints import constraints_from_sdc
         try:
@@ -228,6 +245,15 @@ def main(argv=None):
         print(f"SDC-driven: {sta_loop.plan.K} domains, {n_false} false "
               f"pairs, {n_multi} multicycle pairs (loop cpd = worst "
               f"achieved period)")
+        if sdc_all["io_delays"] or sdc_all["clock_groups"]:
+            n_in = int((np.asarray(cons.launch_extra) > 0).sum()) \
+                if cons.launch_extra is not None else 0
+            n_out = int((np.asarray(cons.capture_extra) > 0).sum()) \
+                if cons.capture_extra is not None else 0
+            n_virt = len(cons.clock_names) - len(
+                getattr(netlist, "clock_names", []) or [])
+            print(f"SDC-driven: {n_in} constrained inputs, {n_out} "
+                  f"constrained outputs, {n_virt} virtual clocks")
 
     # ---- placement ----
     t0 = time.perf_counter()
@@ -385,12 +411,44 @@ def main(argv=None):
                 else res.router.t_sink_delay.cpu().numpy()
             cd3 = cmap3.conn_delays(sd3)
             from .timing.constraints import constraints_from_sdc
-            bc, periods, ps, pm = constraints_from_sdc(sdc_all, netlist)
-            wp, sl, cr = sta.analyze_domains(cd3, bc, periods,
-                                             pair_skip=ps, pair_mult=pm)
+            from .timing.sta import ConstrainedSTA
+            try:
+                cons3 = constraints_from_sdc(sdc_all, netlist)
+                eng3 = None
+                if cons3.launch_extra is not None or args.sdc_report:
+                    eng3 = ConstrainedSTA(netlist, arch, *cons3,
+                                          **cons3.io_kwargs())
+            except ValueError as e:
+                print(f"error: --sdc: {e}", file=sys.stderr)
+                return 2
+            bc, periods, ps, pm = cons3
+            if cons3.launch_extra is not None:
+                wp, sl, cr = eng3.analyze(cd3)
+            else:
+                wp, sl, cr = sta.analyze_domains(cd3, bc, periods,
+                                                 pair_skip=ps, pair_mult=pm)
             ok_sdc = all(wp <= p_ * (1 + 1e-6) for p_ in periods[:1])
             print(f"SDC analysis: worst achieved period {wp*1e9:.3f} ns "
                   f"across {max(1, len(periods))} clock domain(s)")
+            if args.sdc_report:
+                from .timing.report import write_pair_slack_report
+                if args.sdc_driven:
+                    # the loop's own engine, on its last analysis (the
+                    # final delays): the device table with --sta_engine gpu
+                    eng_r = sta_loop
+                else:
+                    eng_r = eng3
+                    if cons3.launch_extra is None:
+                        eng_r.analyze(cd3)
+                n_rows = write_pair_slack_report(
+                    args.sdc_report, eng_r.plan, eng_r.pair_slack(),
+                    cons3.clock_names
+                    or getattr(netlist, "clock_names", None))
+                print(f"wrote {args.sdc_report} ({n_rows} clock pairs)")
+        elif args.sdc_report:
+            print("error: --sdc_report needs an SDC clock and a netlist "
+                  "with clock domains", file=sys.stderr)
+            return 2
         if args.out_verilog or args.out_sdf:
             from .io.verilog import write_verilog, write_sdf
             if args.out_verilog:

@@ -34,14 +34,16 @@ def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu",
     Constraints, a dict with its keys, or a (block_clock, periods,
     pair_skip, pair_mult) tuple). With them the engine is ConstrainedSTA
     ("cpu") or GpuConstrainedSTA over that GpuSTA ("gpu"), and the loops'
-    cpd is the worst achieved period."""
+    cpd is the worst achieved period. The Constraints' launch_extra /
+    capture_extra (SDC I/O delays) go to either engine."""
     if constraints is not None:
         from .timing.constraints import as_constraints
         constraints = as_constraints(constraints)
     if sta_engine == "cpu":
         if constraints is not None:
             from .timing.sta import ConstrainedSTA
-            return ConstrainedSTA(netlist, arch, *constraints)
+            return ConstrainedSTA(netlist, arch, *constraints,
+                                  **constraints.io_kwargs())
         return STA(netlist, arch)
     if sta_engine != "gpu":
         raise ValueError(f"sta_engine must be 'cpu' or 'gpu', "
@@ -52,7 +54,7 @@ def loop_sta(netlist, arch, engine="cpu", sta_engine="cpu",
     if constraints is not None:
         from .timing.gpu_sta import GpuConstrainedSTA
         return GpuConstrainedSTA(GpuSTA(netlist, arch, max_crit=1.0),
-                                 *constraints)
+                                 *constraints, **constraints.io_kwargs())
     return GpuSTA(netlist, arch, max_crit=1.0)
 
 

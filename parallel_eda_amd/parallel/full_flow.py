@@ -60,10 +60,11 @@ def run_flow_gpu(netlist, arch, g, dev_graph=None, rank=0, world_size=1,
         cons = as_constraints(constraints)
         if sta_engine == "gpu":
             from ..timing.gpu_sta import GpuConstrainedSTA
-            loop_sta = GpuConstrainedSTA(loop_sta, *cons)
+            loop_sta = GpuConstrainedSTA(loop_sta, *cons, **cons.io_kwargs())
         else:
             from ..timing.sta import ConstrainedSTA
-            loop_sta = ConstrainedSTA(netlist, arch, *cons)
+            loop_sta = ConstrainedSTA(netlist, arch, *cons,
+                                      **cons.io_kwargs())
     tt = 0.5 if timing_driven else 0.0
 
     t0 = time.perf_counter()

@@ -61,6 +61,7 @@ class StaConstrainedArgs(ct.Structure):
         ("delay", ct.c_void_p), ("slack", ct.c_void_p), ("crit", ct.c_void_p),
         ("worst_bits", ct.c_void_p), ("period_out", ct.c_void_p),
         ("level_start_host", ct.c_void_p),
+        ("launch", ct.c_void_p), ("capture", ct.c_void_p),
     ]
 
 
@@ -74,6 +75,10 @@ def _lib():
         if lib.pnr_sta_constrained_args_sizeof() != \
                 ct.sizeof(StaConstrainedArgs):
             raise RuntimeError("StaConstrainedArgs ABI mismatch")
+        lib.pnr_sta_pair_slack.restype = ct.c_int
+        lib.pnr_sta_pair_slack.argtypes = [ct.POINTER(StaConstrainedArgs),
+                                           ct.c_void_p, ct.c_void_p,
+                                           ct.c_void_p]
         lib.pnr_sta_analyze.restype = ct.c_int
         lib.pnr_sta_analyze.argtypes = [ct.POINTER(StaLaunchArgs), ct.c_void_p]
         lib.pnr_sta_args_sizeof.restype = ct.c_int64
@@ -269,10 +274,18 @@ class GpuConstrainedSTA:
     period, and the uploaded constraint_plan and block_clock. Results
     equal STA.analyze_domains(..., pair_skip, pair_mult) bit for bit (crit
     up to the max_crit clamp; the worst period up to GpuSTA.analyze_domains'
-    tie rule)."""
+    tie rule).
+
+    launch_extra / capture_extra: per-block seconds (SDC I/O delays on
+    pads, timing.constraints); the plan's launch / capture tables are
+    uploaded and read in place of T_seq_out / T_seq_in. Without them the
+    kernels get null tables and the scalars.
+
+    pair_slack() is the report side, outside the loops: the least slack
+    per (source, sink) pair of the last analyze_device()."""
 
     def __init__(self, gsta, block_clock, periods, pair_skip=None,
-                 pair_mult=None):
+                 pair_mult=None, launch_extra=None, capture_extra=None):
         from .constraints import constraint_plan, check_block_clock
         torch = gsta.torch
         self.torch = torch
@@ -281,7 +294,11 @@ class GpuConstrainedSTA:
         self.arch = gsta.arch
         self.netlist = gsta.netlist
         self.max_crit = gsta.max_crit
-        self.plan = plan = constraint_plan(periods, pair_skip, pair_mult)
+        self.plan = plan = constraint_plan(
+            periods, pair_skip, pair_mult, launch_extra=launch_extra,
+            capture_extra=capture_extra, T_seq_out=self.arch.T_seq_out,
+            T_seq_in=self.arch.T_seq_in,
+            block_is_seq=self.netlist.block_is_seq)
         nb = self.netlist.num_blocks
         nc = self.netlist.num_conns
         bc = check_block_clock(block_clock, nb, plan.K)
@@ -304,6 +321,14 @@ class GpuConstrainedSTA:
         self.t_skip = up(plan.skip)
         self.t_req_period = up(plan.req_period)
         self.t_req_domain = up(plan.req_domain)
+        self.t_launch = up(plan.launch) if plan.launch is not None else None
+        self.t_capture = (up(plan.capture) if plan.capture is not None
+                          else None)
+        # pair_slack(): order-preserving bits and the decoded table; the
+        # delay tensor of the last analyze_device is kept alive for it
+        self.t_pair_bits = buf(plan.K * plan.K, torch.int32)
+        self.t_pair_slack = buf(plan.K * plan.K)
+        self._t_delay = None
         self.t_arr = buf(nb * plan.K)
         self.t_req = buf(nb * plan.R)
         self.t_slack = buf(nc)
@@ -350,6 +375,9 @@ class GpuConstrainedSTA:
         a.slack = pt(self.t_slack); a.crit = pt(self.t_crit)
         a.worst_bits = pt(self.t_worst); a.period_out = pt(self.t_period)
         a.level_start_host = g.level_start_host.ctypes.data_as(ct.c_void_p)
+        a.launch = pt(self.t_launch) if self.t_launch is not None else None
+        a.capture = (pt(self.t_capture) if self.t_capture is not None
+                     else None)
         return a
 
     def analyze_device(self, t_conn_delay):
@@ -363,6 +391,7 @@ class GpuConstrainedSTA:
                              f"float32 tensor of {self.netlist.num_conns} "
                              "connection delays")
         self._args.delay = ct.c_void_p(t.data_ptr())
+        self._t_delay = t
         stream = self.torch.cuda.current_stream().cuda_stream
         rc = self.lib.pnr_sta_constrained(ct.byref(self._args), stream)
         hip_api.check(rc, "sta_constrained")
@@ -378,6 +407,23 @@ class GpuConstrainedSTA:
         torch.cuda.synchronize(self.device)
         return (float(self.t_period.item()), self.t_slack.cpu().numpy(),
                 self.t_crit.cpu().numpy())
+
+    def pair_slack(self):
+        """Least slack per (source, sink) clock pair of the last analysis:
+        numpy [K, K] float32, +inf for a false pair or one that reaches no
+        connection; ConstrainedSTA.pair_slack() bit for bit. Two launches
+        (stc_pair_slack, stc_pair_slack_finish) and a synchronisation:
+        for reports, not for the loops. The delay tensor of the last
+        analyze_device must not have been written since."""
+        if self._t_delay is None:
+            raise RuntimeError("pair_slack() needs an analysis first")
+        stream = self.torch.cuda.current_stream().cuda_stream
+        rc = self.lib.pnr_sta_pair_slack(
+            ct.byref(self._args), ct.c_void_p(self.t_pair_bits.data_ptr()),
+            ct.c_void_p(self.t_pair_slack.data_ptr()), stream)
+        hip_api.check(rc, "sta_pair_slack")
+        self.torch.cuda.synchronize(self.device)
+        return self.t_pair_slack.cpu().numpy().reshape(self.K, self.K)
 
     def arr_rows(self):
         """Arrival per (source domain, block), numpy [K, num_blocks]."""

@@ -89,7 +89,13 @@ def parse_sdc_constraints(text):
       false_paths: [(from_clk_or_None, to_clk_or_None)]
       multicycle: [(from_clk_or_None, to_clk_or_None, N)]
       input_delay / output_delay: {clock: seconds}
-    None in a from/to slot means 'all clocks' (SDC wildcard)."""
+      io_delays: [(kind, clock, seconds, patterns)] in file order; kind
+        "input" / "output", patterns the get_ports list (regular
+        expressions) or None for all ports of that direction
+      clock_groups: one list of name lists per
+        set_clock_groups -exclusive -group {A B} -group {C} line
+    None in a from/to slot means 'all clocks' (SDC wildcard).
+    set_max_delay is not supported."""
     import re
 
     def clk_arg(rest, flag):
@@ -101,10 +107,17 @@ def parse_sdc_constraints(text):
         return m.group(1) if m else None
 
     out = dict(clocks=parse_sdc_clocks(text), false_paths=[],
-               multicycle=[], input_delay={}, output_delay={})
+               multicycle=[], input_delay={}, output_delay={},
+               io_delays=[], clock_groups=[])
     for line in text.splitlines():
         line = line.split("#", 1)[0].strip()
-        if line.startswith("set_false_path"):
+        if line.startswith("set_clock_groups"):
+            grps = [(m.group(1) if m.group(1) is not None
+                     else m.group(2)).split() for m in
+                    re.finditer(r"-group\s+(?:\{([^}]*)\}|(\S+))", line)]
+            if grps:
+                out["clock_groups"].append(grps)
+        elif line.startswith("set_false_path"):
             out["false_paths"].append((clk_arg(line, "-from"),
                                        clk_arg(line, "-to")))
         elif line.startswith("set_multicycle_path"):
@@ -118,9 +131,55 @@ def parse_sdc_constraints(text):
             v = re.search(r"(?:-clock\s+\S+\s+|\]\s+)([0-9.eE+-]+)", line)
             key = ("input_delay" if line.startswith("set_input") else
                    "output_delay")
+            io = _io_delay_line(line, out["clocks"])
+            if io:
+                out["io_delays"].append(io)
             if c and v:
-                out[key][c] = float(v.group(1)) * 1e-9
+                try:
+                    out[key][c] = float(v.group(1)) * 1e-9
+                except ValueError:      # a flag such as -max before V
+                    if io:
+                        out[key][c] = io[2]
     return out
+
+
+def _io_delay_line(line, clocks):
+    """(kind, clock, seconds, patterns) of one set_input_delay /
+    set_output_delay -clock C [-max] V [get_ports {p ...}] line, or None
+    if it has no clock or no value, or is a -min line. patterns is None
+    without get_ports (all ports of that direction); with exactly one
+    create_clock, -clock * names it (reference read_sdc.c)."""
+    import re
+    kind = "input" if line.startswith("set_input_delay") else "output"
+    patterns = None
+    gp = re.search(r"\[\s*get_ports\s+\{?([^\}\]]*)\}?\s*\]", line)
+    if gp:
+        patterns = gp.group(1).split()
+        line = line[:gp.start()] + " " + line[gp.end():]
+    line = re.sub(r"\[\s*get_clocks\s+\{?\s*(\S+?)\s*\}?\s*\]", r"\1", line)
+    tok = line.split()[1:]
+    if "-min" in tok:                   # setup analysis only
+        return None
+    clock = value = None
+    i = 0
+    while i < len(tok):
+        if tok[i] == "-clock" and i + 1 < len(tok):
+            clock = tok[i + 1]
+            i += 2
+            continue
+        if not tok[i].startswith("-") or \
+                re.fullmatch(r"-[0-9.]+(?:[eE][+-]?\d+)?", tok[i]):
+            if value is None:
+                try:
+                    value = float(tok[i])
+                except ValueError:
+                    return None
+        i += 1
+    if clock is None or value is None:
+        return None
+    if clock == "*" and len(clocks) == 1:
+        clock = next(iter(clocks))
+    return (kind, clock, value * 1e-9, patterns)
 
 
 def pair_constraints(sdc, clock_names):
@@ -146,6 +205,32 @@ def pair_constraints(sdc, clock_names):
             for j in rows(t):
                 mult[i, j] = float(n)
     return skip, mult
+
+
+def write_pair_slack_report(path, plan, pair_slack, clock_names=None):
+    """One line per analysed (source, sink) clock pair: source clock, sink
+    clock, setup constraint and worst slack, in ns (the reference prints
+    the least slack per constraint). plan: the engine's constraint_plan;
+    pair_slack: its [K, K] table (ConstrainedSTA.pair_slack() or
+    GpuConstrainedSTA.pair_slack()); a pair with +inf (false, or reaching
+    no connection) is not listed. Returns the number of pairs written."""
+    K = plan.K
+    names = list(clock_names or [])
+    names += [f"domain{i}" for i in range(len(names), K)]
+    ps = np.asarray(pair_slack, dtype=np.float32).reshape(K, K)
+    cons = np.asarray(plan.cons, dtype=np.float32).reshape(K, K)
+    n = 0
+    with open(path, "w") as f:
+        f.write("# source_clock sink_clock constraint_ns worst_slack_ns\n")
+        for ci in range(K):
+            for cj in range(K):
+                if not np.isfinite(ps[ci, cj]):
+                    continue
+                f.write(f"{names[ci]} {names[cj]} "
+                        f"{float(cons[ci, cj]) * 1e9:.4f} "
+                        f"{float(ps[ci, cj]) * 1e9:.4f}\n")
+                n += 1
+    return n
 
 
 def parse_sdc_clocks(text):
