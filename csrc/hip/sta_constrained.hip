@@ -1,13 +1,15 @@
-// CDNA4 constrained multi-clock STA: the (source, sink) clock-pair analysis
-// of sta_kernel.hip's pnr_sta_analyze_domains with SDC false paths and
-// multicycle paths, shaped for the place and route loops: one launch per
-// level for all domains, no host round trip, nothing synchronised.
+// CDNA4 multi-clock STA: the (source, sink) clock-pair analysis, with SDC
+// false paths and multicycle paths, shaped for the place and route loops:
+// one launch per level for all domains, no host round trip, nothing
+// synchronised. The unconstrained analysis is the trivial plan (one backward
+// row per sink domain, no false pair, constraint = the sink's period).
 //
 // Reference semantics: csrc/cpu/sta_serial.cpp analyze_domains (pair_skip /
-// pair_mult; do_timing_analysis_new's domain-pair loop, read_sdc.c). The
-// arithmetic per (block, domain) and per (connection, pair) is that of
-// sta_fwd_domain_level / sta_bwd_domain_level / sta_slack_domains, operation
-// for operation; only the launch shape and the data layout differ.
+// pair_mult; do_timing_analysis_new's (src, sink)-domain-pair loop,
+// path_delay.c:1996-2085, read_sdc.c). Per source domain a forward max-plus
+// sweep of arrivals, per (sink domain, period) row a backward min-minus sweep
+// of required times, level by level, then one (connection, pair) pass for
+// the worst slack and the largest criticality per connection.
 //
 // Layout: arr[b * K + ci], req[b * R + row] (block-major, rows interleaved).
 // One thread per (block of the level, row) with the row fastest, so the K
@@ -140,14 +142,30 @@ __device__ __forceinline__ bool stc_conn_pair_slack(
   return true;
 }
 
-// order-preserving bits of a float: unsigned order = float order
+// order-preserving bits of a float: unsigned order = float order. Slack can
+// be negative, so a negative value has all its bits flipped and a
+// non-negative one its sign bit set. All-ones (the 0xFF fill) is above the
+// bits of +inf, so no atomicMin of a slack leaves it in place: it is the
+// sentinel "no pair analysed here". The finish kernels test for it before
+// they decode: a connection's slack becomes 0 (stc_finish), a pair's least
+// slack +inf (stc_pair_slack_finish).
 __device__ __forceinline__ unsigned stc_order_bits(float v) {
   unsigned b = __float_as_uint(v);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// the inverse of stc_order_bits
+__device__ __forceinline__ float stc_order_value(unsigned b) {
+  return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
+}
+
 // one thread per (conn, ci, cj): worst slack / max criticality per conn and
-// the packed worst achieved period (see sta_slack_domains)
+// the worst achieved period. The worst period is the achieved period of the
+// largest achieved / constraint ratio, tracked as one 64-bit max on
+// (ratio bits << 32) | achieved bits, so the period always belongs to the
+// winning ratio and the result depends on neither launch shape nor order.
+// Both halves are non-negative floats (bit order = value order); equal
+// ratios keep the larger period. A high half of 0 means no pair analysed.
 __global__ void stc_pairs(StcDev s, const float* __restrict__ delay,
                           float* slack, float* crit,
                           unsigned long long* worst) {
@@ -187,9 +205,7 @@ __global__ void stc_finish(int64_t num_conns, float* slack,
   }
   for (; c < num_conns; c += (int64_t)gridDim.x * blockDim.x) {
     unsigned sb = __float_as_uint(slack[c]);
-    if (sb == 0xFFFFFFFFu) { slack[c] = 0.0f; continue; }
-    sb = (sb & 0x80000000u) ? (sb & 0x7FFFFFFFu) : ~sb;
-    slack[c] = __uint_as_float(sb);
+    slack[c] = (sb == 0xFFFFFFFFu) ? 0.0f : stc_order_value(sb);
   }
 }
 
@@ -228,9 +244,8 @@ __global__ void stc_pair_slack_finish(int32_t KK, const unsigned* bits,
   int32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= KK) return;
   unsigned sb = bits[p];
-  if (sb == 0xFFFFFFFFu) { out[p] = __uint_as_float(0x7F800000u); return; }
-  sb = (sb & 0x80000000u) ? (sb & 0x7FFFFFFFu) : ~sb;
-  out[p] = __uint_as_float(sb);
+  out[p] = (sb == 0xFFFFFFFFu) ? __uint_as_float(0x7F800000u)
+                               : stc_order_value(sb);
 }
 
 }  // namespace pnrh

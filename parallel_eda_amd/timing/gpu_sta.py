@@ -1,9 +1,10 @@
 """GPU STA: levelized slack/criticality sweeps as HIP kernels.
 
-Host side of csrc/hip/sta_kernel.hip. Graph topology (levels + CSRs) is
-built once by the C++ TimingGraph and uploaded; per-iteration analysis
-takes a device conn-delay tensor and produces device slack/crit tensors
-(cpd returned to host).
+Host side of csrc/hip/sta_kernel.hip (single clock, GpuSTA) and
+csrc/hip/sta_constrained.hip (clock domains, GpuConstrainedSTA). Graph
+topology (levels + CSRs) is built once by the C++ TimingGraph and
+uploaded; per-iteration analysis takes a device conn-delay tensor and
+produces device slack/crit tensors (cpd returned to host).
 """
 import ctypes as ct
 
@@ -28,16 +29,6 @@ class StaLaunchArgs(ct.Structure):
         ("t_arr", ct.c_void_p), ("t_req", ct.c_void_p), ("cpd_out", ct.c_void_p),
         ("delay", ct.c_void_p), ("slack", ct.c_void_p), ("crit", ct.c_void_p),
         ("level_start_host", ct.c_void_p),
-    ]
-
-
-class StaDomainsArgs(ct.Structure):
-    _fields_ = [
-        ("base", StaLaunchArgs),
-        ("block_clock", ct.c_void_p), ("periods", ct.c_void_p),
-        ("K", ct.c_int32),
-        ("arr_all", ct.c_void_p), ("req_all", ct.c_void_p),
-        ("worst_bits", ct.c_void_p),
     ]
 
 
@@ -84,17 +75,19 @@ def _lib():
         lib.pnr_sta_args_sizeof.restype = ct.c_int64
         if lib.pnr_sta_args_sizeof() != ct.sizeof(StaLaunchArgs):
             raise RuntimeError("StaLaunchArgs ABI mismatch")
-        lib.pnr_sta_analyze_domains.restype = ct.c_int
-        lib.pnr_sta_analyze_domains.argtypes = [ct.POINTER(StaDomainsArgs),
-                                                ct.c_void_p]
-        lib.pnr_sta_domains_args_sizeof.restype = ct.c_int64
-        if lib.pnr_sta_domains_args_sizeof() != ct.sizeof(StaDomainsArgs):
-            raise RuntimeError("StaDomainsArgs ABI mismatch")
         lib._sta_ready = True
     return lib
 
 
 class GpuSTA:
+    """Single-clock analysis as a loop engine (csrc/hip/sta_kernel.hip) and
+    the owner of the device timing graph: levels, CSRs and per-block delays
+    are uploaded once here and shared by every GpuConstrainedSTA built on
+    it. analyze_device() takes a device delay tensor and leaves cpd, slack
+    and crit in t_cpd / t_slack / t_crit, with no allocation, host copy or
+    synchronisation. Clock domains are GpuConstrainedSTA's;
+    analyze_domains() is the one-call form of it."""
+
     def __init__(self, netlist, arch: ArchDef, device="cuda:0", max_crit=0.99):
         import torch
         self.torch = torch
@@ -136,14 +129,13 @@ class GpuSTA:
         self.t_slack = torch.zeros(nc, dtype=torch.float32, device=device)
         self.t_crit = torch.zeros(nc, dtype=torch.float32, device=device)
         self.lib = _lib()
+        self._args = self._build_args()
 
     @property
     def num_conns(self):
         return self.netlist.num_conns
 
-    def analyze_device(self, t_conn_delay):
-        """Device path: conn delays in, (cpd, slack_t, crit_t) out
-        (slack/crit stay on device)."""
+    def _build_args(self):
         a = StaLaunchArgs()
         pt = lambda t: ct.c_void_p(t.data_ptr())
         a.level_blocks = pt(self.t_level_blocks)
@@ -162,11 +154,16 @@ class GpuSTA:
         a.num_conns = self.netlist.num_conns
         a.t_arr = pt(self.t_arr); a.t_req = pt(self.t_req)
         a.cpd_out = pt(self.t_cpd)
-        a.delay = pt(t_conn_delay); a.slack = pt(self.t_slack)
-        a.crit = pt(self.t_crit)
+        a.slack = pt(self.t_slack); a.crit = pt(self.t_crit)
         a.level_start_host = self.level_start_host.ctypes.data_as(ct.c_void_p)
+        return a
+
+    def analyze_device(self, t_conn_delay):
+        """Device path: conn delays in, (cpd, slack_t, crit_t) out
+        (slack/crit stay on device)."""
+        self._args.delay = ct.c_void_p(t_conn_delay.data_ptr())
         stream = self.torch.cuda.current_stream().cuda_stream
-        rc = self.lib.pnr_sta_analyze(ct.byref(a), stream)
+        rc = self.lib.pnr_sta_analyze(ct.byref(self._args), stream)
         hip_api.check(rc, "sta_analyze")
         return self.t_cpd, self.t_slack, self.t_crit
 
@@ -183,70 +180,13 @@ class GpuSTA:
         (source, sink) pair both engines return periods[0].
 
         pair_skip / pair_mult: KxK false-pair and multicycle arrays as in
-        STA.analyze_domains. With either given the analysis runs through a
-        temporary GpuConstrainedSTA (pnr_sta_constrained); with both None
-        it is pnr_sta_analyze_domains, the second implementation the
-        constrained kernels are compared with."""
-        if pair_skip is not None or pair_mult is not None:
-            return GpuConstrainedSTA(self, block_clock, periods, pair_skip,
-                                     pair_mult).analyze(conn_delay)
-        torch = self.torch
-        K = len(periods)
-        nb = self.netlist.num_blocks
-        t_delay = torch.from_numpy(
-            np.ascontiguousarray(conn_delay, dtype=np.float32)).to(self.device)
-        t_bc = torch.from_numpy(
-            np.ascontiguousarray(block_clock, dtype=np.int32)).to(self.device)
-        t_per = torch.from_numpy(
-            np.ascontiguousarray(periods, dtype=np.float32)).to(self.device)
-        t_arr_all = torch.zeros(K * nb, dtype=torch.float32,
-                                device=self.device)
-        t_req_all = torch.zeros(K * nb, dtype=torch.float32,
-                                device=self.device)
-        # (ratio bits << 32) | achieved-period bits, see sta_slack_domains
-        t_worst = torch.zeros(1, dtype=torch.int64, device=self.device)
-        d = StaDomainsArgs()
-        d.base = self._base_args(t_delay)
-        pt = lambda t: ct.c_void_p(t.data_ptr())
-        d.block_clock = pt(t_bc); d.periods = pt(t_per); d.K = K
-        d.arr_all = pt(t_arr_all); d.req_all = pt(t_req_all)
-        d.worst_bits = pt(t_worst)
-        stream = self.torch.cuda.current_stream().cuda_stream
-        rc = self.lib.pnr_sta_analyze_domains(ct.byref(d), stream)
-        hip_api.check(rc, "sta_analyze_domains")
-        torch.cuda.synchronize(self.device)
-        packed = int(t_worst.item())
-        if packed >> 32 == 0:  # no pair analysed (the CPU engine's start)
-            worst = float(np.float32(periods[0]))
-        else:
-            worst = float(np.asarray([packed & 0xFFFFFFFF],
-                                     dtype=np.uint32).view(np.float32)[0])
-        return (worst, self.t_slack.cpu().numpy(),
-                self.t_crit.cpu().numpy())
-
-    def _base_args(self, t_conn_delay):
-        a = StaLaunchArgs()
-        pt = lambda t: ct.c_void_p(t.data_ptr())
-        a.level_blocks = pt(self.t_level_blocks)
-        a.level_start = pt(self.t_level_start)
-        a.in_ptr = pt(self.t_in_ptr); a.in_conn = pt(self.t_in_conn)
-        a.out_ptr = pt(self.t_out_ptr); a.out_conn = pt(self.t_out_conn)
-        a.conn_driver = pt(self.t_conn_driver)
-        a.conn_sink = pt(self.t_conn_sink)
-        a.is_seq = pt(self.t_is_seq)
-        a.blk_delay = (pt(self.t_blk_delay)
-                       if self.t_blk_delay is not None else None)
-        a.T_clb = self.arch.T_clb; a.T_seq_out = self.arch.T_seq_out
-        a.T_seq_in = self.arch.T_seq_in; a.max_crit = self.max_crit
-        a.num_blocks = self.netlist.num_blocks
-        a.num_levels = self.num_levels
-        a.num_conns = self.netlist.num_conns
-        a.t_arr = pt(self.t_arr); a.t_req = pt(self.t_req)
-        a.cpd_out = pt(self.t_cpd)
-        a.delay = pt(t_conn_delay); a.slack = pt(self.t_slack)
-        a.crit = pt(self.t_crit)
-        a.level_start_host = self.level_start_host.ctypes.data_as(ct.c_void_p)
-        return a
+        STA.analyze_domains; None means no false pair / every multiplier 1.
+        One call of a temporary GpuConstrainedSTA (pnr_sta_constrained),
+        which validates block_clock and periods (ValueError) and owns
+        every buffer it writes: this engine's single-clock results
+        (t_arr, t_req, t_slack, t_crit, t_cpd) are left as they are."""
+        return GpuConstrainedSTA(self, block_clock, periods, pair_skip,
+                                 pair_mult).analyze(conn_delay)
 
     def analyze(self, conn_delay):
         """Host-compatible API (numpy in/out), mirroring timing.sta.STA
@@ -261,9 +201,10 @@ class GpuSTA:
 
 
 class GpuConstrainedSTA:
-    """Multi-clock analysis under false-path and multicycle constraints as
-    a loop engine (csrc/hip/sta_constrained.hip): analyze_device() takes a
-    device delay tensor and leaves the worst achieved period, slack and
+    """The multi-clock analysis, with or without false-path and multicycle
+    constraints, as a loop engine (csrc/hip/sta_constrained.hip; pair_skip
+    and pair_mult None give the plain clock-pair analysis):
+    analyze_device() takes a device delay tensor and leaves the worst achieved period, slack and
     crit on the device with no allocation, host copy or synchronisation,
     so timing.device_loop drives it like a GpuSTA.
 
@@ -273,8 +214,9 @@ class GpuConstrainedSTA:
     row by row), slack, crit, the packed worst word, the float32[1]
     period, and the uploaded constraint_plan and block_clock. Results
     equal STA.analyze_domains(..., pair_skip, pair_mult) bit for bit (crit
-    up to the max_crit clamp; the worst period up to GpuSTA.analyze_domains'
-    tie rule).
+    up to the max_crit clamp; among equal achieved/constraint ratios the
+    worst period is the larger one, where the CPU engine keeps the first
+    it meets).
 
     launch_extra / capture_extra: per-block seconds (SDC I/O delays on
     pads, timing.constraints); the plan's launch / capture tables are

@@ -571,11 +571,11 @@ def test_gpu_engine_reuse_no_allocation():
 def test_gpu_analyze_domains_pair_arguments(name):
     cs, dm = case(name), domains(name)
     gs = _gsta(cs, 1.0)
-    # both None: today's entry point, today's result
+    # both None: the plain clock-pair analysis
     wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
-    _same_bits(slack, dm.slack, "old entry slack")
-    _same_bits(crit, dm.crit, "old entry crit")
-    _same_bits(F(wp), F(dm.wp), "old entry period")
+    _same_bits(slack, dm.slack, "no pair argument: slack")
+    _same_bits(crit, dm.crit, "no pair argument: crit")
+    _same_bits(F(wp), F(dm.wp), "no pair argument: period")
     for set_name in ("false01", "mc_shared", "false_and_mc", "all_false"):
         e = expected(name, set_name)
         wp, slack, crit = gs.analyze_domains(e.d, e.bc, e.periods,
@@ -587,11 +587,11 @@ def test_gpu_analyze_domains_pair_arguments(name):
             assert float(F(wp)) in e.rp.top
         else:
             assert F(wp) == e.periods[0]
-    # the two device implementations agree without constraints
+    # explicit unit multipliers and None give the same bits
     e = expected(name, "none")
     ones = np.ones((K, K), F)
     wp_n, slack_n, crit_n = gs.analyze_domains(dm.d, dm.bc, dm.periods,
                                                pair_mult=ones)
-    _same_bits(slack_n, dm.slack, "new entry, no constraint: slack")
-    _same_bits(crit_n, dm.crit, "new entry, no constraint: crit")
-    _same_bits(F(wp_n), F(dm.wp), "new entry, no constraint: period")
+    _same_bits(slack_n, dm.slack, "unit multipliers: slack")
+    _same_bits(crit_n, dm.crit, "unit multipliers: crit")
+    _same_bits(F(wp_n), F(dm.wp), "unit multipliers: period")

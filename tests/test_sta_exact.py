@@ -1,4 +1,5 @@
-"""GPU STA kernels (csrc/hip/sta_kernel.hip) against exact host models.
+"""GPU STA kernels (csrc/hip/sta_kernel.hip; GpuSTA.analyze_domains is
+csrc/hip/sta_constrained.hip) against exact host models.
 
 Every value the forward, cpd, backward and slack kernels produce is a chain
 of single fp32 `+`, `-`, `max`, `min`, and max/min do not depend on the
@@ -637,6 +638,47 @@ def test_gpu_state_reuse(name):
         _same_bits(F(wp), F(dm.wp), "worst period after NaN prefill")
 
 
+@gpu
+def test_gpu_domains_leave_single_clock_buffers():
+    """analyze_domains owns what it writes: the single-clock results of the
+    same GpuSTA keep every bit across a domain call."""
+    cs, dm = case("wide_het"), domains("wide_het")
+    gs = _gsta(cs, 1.0)
+    gs.analyze(cs.delays["rand"])
+    names = ("t_arr", "t_req", "t_slack", "t_crit", "t_cpd")
+    before = [getattr(gs, n).cpu().numpy().copy() for n in names]
+    wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
+    for n, b in zip(names, before):
+        _same_bits(getattr(gs, n).cpu().numpy(), b,
+                   f"{n} after analyze_domains")
+    _same_bits(slack, dm.slack, "domain slack")
+    _same_bits(crit, dm.crit, "domain crit")
+    _same_bits(F(wp), F(dm.wp), "worst period")
+
+
+@gpu
+def test_gpu_domains_refuse_bad_input():
+    """Unconstrained calls are validated on the host, before anything is
+    enqueued, and a refusal leaves the GpuSTA usable."""
+    cs = case("chain")
+    d = cs.delays["rand"]
+    gs = _gsta(cs, 1.0)
+    bc = np.asarray([0, 1, -1, -1], np.int32)
+    periods = np.asarray([2e-9, 3e-9, 5e-9], F)
+    with pytest.raises(ValueError):
+        gs.analyze_domains(d, bc, np.full(65, 2e-9, F))
+    with pytest.raises(ValueError):
+        gs.analyze_domains(d, np.asarray([0, 3, -1, -1], np.int32), periods)
+    with pytest.raises(ValueError):
+        gs.analyze_domains(d, bc[:3], periods)
+    wp_c, sl_c, cr_c = cs.sta.analyze_domains(d, bc, periods)
+    assert (sl_c != 0).any()          # a pair is analysed
+    wp, slack, crit = gs.analyze_domains(d, bc, periods)
+    _same_bits(slack, sl_c, "slack after the refusals")
+    _same_bits(crit, cr_c, "crit after the refusals")
+    _same_bits(F(wp), F(wp_c), "worst period after the refusals")
+
+
 # -------------------------------------------------------- GPU: multi-domain
 
 @gpu
@@ -645,7 +687,7 @@ def test_gpu_domains_exact(name):
     cs, dm = case(name), domains(name)
     for max_crit in (1.0, 0.99):
         gs = _gsta(cs, max_crit)
-        for rep in range(2):     # the second call reuses slack/crit
+        for rep in range(2):     # the same answer call after call
             wp, slack, crit = gs.analyze_domains(dm.d, dm.bc, dm.periods)
             tag = f"{name}/max_crit={max_crit}/call {rep}"
             _same_bits(slack, dm.slack, f"{tag} slack")
