@@ -104,6 +104,19 @@ __device__ __forceinline__ uint64_t load_state(const uint64_t* p) {
                            __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Start cost of a tree seed. A seed's state word is (0.0, self), which
+// only a word of cost exactly 0.0 and a smaller prev can undercut. SOURCE->
+// OPIN hops have zero delay, so at crit 1 (or from a seed of cost 0) a
+// relaxation out of the root would carry (0.0, source) into an OPIN already
+// in the tree and the next path would run through the tree. Starting every
+// seed at the smallest normal float or above keeps every back cost
+// positive (sums of non-negative terms never fall below their first), and
+// it is absorbed by the first real hop: 1.2e-38 against delays of 1e-11
+// and base costs of 1.
+__device__ __forceinline__ float seed_back(float crit, float delay) {
+  return fmaxf(crit * delay, __FLT_MIN__);
+}
+
 struct SinkCtx {
   int32_t sink_node;
   int16_t sx, sy;

@@ -261,7 +261,7 @@ __global__ void route_nets_cal_kernel(
         int32_t v = t_node[k];
         if (g.type[v] == 1) continue;
         if (!L.in_bb(g, v)) continue;
-        float back = S.crit * t_delay[k];
+        float back = seed_back(S.crit, t_delay[k]);
         float tot = back + S.astar_fac * expected_cost(g, P, v, S);
         int64_t li = L(g, v);
         state[li] = pack_state(0.0f, v);

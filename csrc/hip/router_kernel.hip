@@ -273,15 +273,15 @@ __global__ void route_nets_kernel(
 #endif
         if (g.type[v] == 1 /*SINK*/) continue;
         if (!L.in_bb(g, v)) continue;
-        float back = S.crit * t_delay[k];
+        float back = seed_back(S.crit, t_delay[k]);
         float tot = back + S.astar_fac * expected_cost(g, P, v, S);
         int64_t li = L(g, v);
         // prev==self marks a tree seed; stored back 0.0 makes the seed
-        // UNBEATABLE by any ordinary entry (all edge costs > 0), so the
-        // backtrack's prev==self stop condition is stable and a path can
-        // never re-enter the tree (which would duplicate tree nodes and
-        // leave phantom occupancy). The frontier entry carries the REAL
-        // back cost for expansion.
+        // unbeatable by any entry of positive cost, and seed_back() keeps
+        // every cost positive, so the backtrack's prev==self stop
+        // condition is stable and a path can never re-enter the tree
+        // (which would duplicate tree nodes and leave phantom occupancy).
+        // The frontier entry carries the REAL back cost for expansion.
         state[li] = pack_state(0.0f, v);
         inq[li] = 1;
         int ti = atomicAdd(&sh.touched_cnt, 1);
@@ -306,8 +306,10 @@ __global__ void route_nets_kernel(
         if (n_cur == 0) { if (tid == 0 && sh.best_sink_back == 0xffffffffu) sh.fail = FAIL_NO_PATH; break; }
         // terminate when the sink's settled cost beats the min frontier f.
         // Deterministic mode uses STRICT <: the == bucket must be fully
-        // processed so equal-cost tie-breaks reach their fixpoint (with an
-        // admissible heuristic the result is then order-independent).
+        // processed so equal-cost tie-breaks reach their fixpoint. The
+        // result is then order-independent at astar_fac 0; expected_cost
+        // is not admissible (docs/KERNELS.md, "What is exact"), so at
+        // astar_fac 1 that does not follow.
         // Normal mode uses <= — at pres_fac 0 the fabric is full of exact
         // cost ties and processing every tie plateau explodes the frontier.
         if (sh.best_sink_back != 0xffffffffu &&

@@ -91,7 +91,7 @@ __global__ void mwg_seed_kernel(RRDev g, NetsDev nets, TreesDev trees,
     int32_t v = trees.node[off + i];
     if (g.type[v] == 1 /*SINK*/) continue;
     if (!L.in_bb(g, v)) continue;
-    float back = S.crit * trees.delay[off + i];
+    float back = seed_back(S.crit, trees.delay[off + i]);
     float tot = back + S.astar_fac * expected_cost(g, P, v, S);
     state[v] = pack_state(0.0f, v);   // seed: unbeatable, prev==self
     inq[v] = 1;

@@ -140,9 +140,13 @@ class GpuRouter:
         import os as _os
         astar_fac = float(_os.environ.get("PNR_ASTAR", astar_fac))
         delta_fac = float(_os.environ.get("PNR_DELTA", delta_fac))
-        # deterministic mode needs an ADMISSIBLE lookahead (astar_fac<=1):
-        # with an inflated heuristic the termination point depends on
-        # which paths the racing relaxations discovered first
+        # deterministic mode clamps astar_fac to 1: with an inflated
+        # heuristic the termination point depends on which paths the
+        # racing relaxations discovered first. The clamp does NOT make the
+        # lookahead admissible (it overestimates wires by one segment and
+        # sink-tile IPINs by the IPIN term, docs/KERNELS.md "What is
+        # exact"), so order-independence is only implied at astar_fac = 0;
+        # at 1 a path may be up to eps above the optimum.
         self.astar_fac = min(astar_fac, 1.0) if deterministic else astar_fac
         self.bb_margin = bb_margin
         self.max_rounds = max_rounds
