@@ -16,12 +16,14 @@
 // Each phase exists once (propose_move, resolve_move, apply_move). Two
 // drivers run it and must agree to the bit (tests/test_gpu_place_run.py):
 //   pnr_place_batch  reset, propose, resolve, apply: four launches, stop
-//                    rule on the host, MinClaims. Kept as the oracle.
+//                    rule on the host, MinClaims, DirectCounters. Kept as
+//                    the oracle.
 //   pnr_place_run    propose, then resolve + apply fused into one commit
 //                    launch; stop rule on the device, EpochClaims (no
-//                    reset); many batches per call.
-// They differ in the claim policy, the launches and the stop rule only
-// (docs/KERNELS.md, placer section).
+//                    reset), ShardCounters folded by the stop rule; many
+//                    batches per call.
+// They differ in the claim policy, the counter policy, the launches and
+// the stop rule only (docs/KERNELS.md, placer section).
 #include "pnr_hip.h"
 
 namespace pnrh {
@@ -72,7 +74,10 @@ struct MovesDev {
   int32_t* net_claim;   // [num_nets] MinClaims words (pnr_place_batch)
   int32_t* loc_claim;   // [gx*gy] the same, tile granularity
   int32_t* counters;    // [4]: attempts, accepted, winners, conflicts, over
-                        // all batches of a run_batches call (host zeroes)
+                        // all batches of a run_batches call (host zeroes).
+                        // pnr_place_batch adds to them directly; in
+                        // pnr_place_run they are the totals that the stop
+                        // rule folds from the shards (see ShardCounters)
   // stored costs [n_moves x cost_k]: what propose found net_cost and
   // net_tcost of an accepted single move's nets to be after the move.
   // Slot k is the k-th net of blk, slot nets(blk) + k the k-th of other;
@@ -257,6 +262,31 @@ struct EpochClaims {
 __device__ __forceinline__ unsigned long long claim_key(uint32_t batch, int i) {
   return ((unsigned long long)batch << 32) | (0xFFFFFFFFu - (uint32_t)i);
 }
+
+// ---- counter policies ------------------------------------------------
+// Every valid proposal, accepted move and verdict counts one, from lane 0.
+// Integer sums do not depend on order, so both policies give the same
+// totals.
+enum { CNT_ATTEMPTS = 0, CNT_ACCEPTED = 1, CNT_WINNERS = 2, CNT_CONFLICTS = 3 };
+// DirectCounters (pnr_place_batch): the four words of MovesDev::counters,
+// which the host reads after a synchronise.
+struct DirectCounters {
+  int32_t* w;
+  __device__ __forceinline__ void add(int k) const { atomicAdd(&w[k], 1); }
+};
+// ShardCounters (pnr_place_run): S shards (a power of two), each a 128-byte
+// line of its own that holds the shard's four counters in its first words.
+// A workgroup adds to shard blockIdx.x & (S - 1), so a line queues the
+// atomics of n_workgroups / S workgroups and not of the whole launch. The
+// stop rule of place_commit_kernel folds the shards into
+// MovesDev::counters.
+#define SHARD_WORDS 32   // int32 words of a 128-byte line
+struct ShardCounters {
+  int32_t* w;   // this workgroup's shard
+  __device__ __forceinline__ ShardCounters(int32_t* shards, int32_t mask)
+      : w(shards + (int64_t)(blockIdx.x & mask) * SHARD_WORDS) {}
+  __device__ __forceinline__ void add(int k) const { atomicAdd(&w[k], 1); }
+};
 
 // ---- propose -------------------------------------------------------
 // lane-0 candidate selection (same RNG stream as the round-1 per-thread
@@ -535,11 +565,11 @@ bool metropolis(const Sched& s, int i, float& dbb, float& dtd) {
 // lane 0 records an accepted move for resolve and apply. `from` is the
 // proposer's source tile: resolve must not read it from bx/by, which the
 // winners of a fused commit launch are rewriting.
-__device__ __forceinline__
-void record_move(const MovesDev& m, int32_t* mv_from, int i, int32_t blk,
-                 int32_t to, int32_t other, float dbb, float dtd,
-                 int32_t from) {
-  atomicAdd(&m.counters[1], 1);
+template <class Counters> __device__ __forceinline__
+void record_move(const MovesDev& m, const Counters& cnt, int32_t* mv_from,
+                 int i, int32_t blk, int32_t to, int32_t other, float dbb,
+                 float dtd, int32_t from) {
+  cnt.add(CNT_ACCEPTED);
   m.mv_blk[i] = blk;
   m.mv_to[i] = to;
   m.mv_other[i] = other;
@@ -555,9 +585,10 @@ void record_move(const MovesDev& m, int32_t* mv_from, int i, int32_t blk,
 // affected nets' exact deltas in parallel and reduces them, and claims
 // go out lane-strided (taking a claim is idempotent, so the block lists
 // need no dedup — only the delta sum skips shared nets).
-template <class Claims> __device__ __forceinline__
+template <class Claims, class Counters> __device__ __forceinline__
 void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
-                  int32_t* mv_from, int i, const Sched& s) {
+                  const Counters& cnt, int32_t* mv_from, int i,
+                  const Sched& s) {
   const int lane = threadIdx.x & 63;
   int sel = -1, sx1 = -1, sy1 = -1, sslot = 0;
   if (lane == 0) {
@@ -581,7 +612,7 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
     int ok = 0;
     if (lane == 0) {
       ok = macro_shift_ok(p, ms, mm0, mm1);
-      if (ok) atomicAdd(&m.counters[0], 1);
+      if (ok) cnt.add(CNT_ATTEMPTS);
     }
     ok = __shfl(ok, 0);
     if (!ok) return;
@@ -594,7 +625,7 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
     });
     if (!metropolis(s, i, dbb, dtd)) return;
     if (lane == 0)
-      record_move(m, mv_from, i, blk,
+      record_move(m, cnt, mv_from, i, blk,
                   ((ms.ddx + 4096) << 13) | (ms.ddy + 4096), -2 - mid, dbb,
                   dtd, x0 * p.gy + y0);
     for_macro_nets(p, mm0, mm1, [&](int32_t, int32_t n) { c.take_net(n); });
@@ -611,7 +642,7 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
   if (other >= 0 && p.fixed && p.fixed[other]) return;
   if (other >= 0 && p.macro_of && p.macro_of[other] >= 0)
     return;   // never swap a chain member out from under its macro
-  if (lane == 0) atomicAdd(&m.counters[0], 1);  // valid proposals only
+  if (lane == 0) cnt.add(CNT_ATTEMPTS);  // valid proposals only
   // nets shared by both blocks are counted once (skipped in other's pass)
   const SwapPos sw{blk, x1, y1, other, other >= 0 ? x0 : -1000,
                    other >= 0 ? y0 : -1000};
@@ -653,7 +684,7 @@ void propose_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
     }
   }
   if (lane == 0) {
-    record_move(m, mv_from, i, blk,
+    record_move(m, cnt, mv_from, i, blk,
                 ((x1 * p.gy + y1) * p.cap + slot1) |
                     (stored ? 0 : MV_RECOMPUTE),
                 other, dbb, dtd, x0 * p.gy + y0);
@@ -689,9 +720,10 @@ struct Move {
 // winning proposal of the same chain may point off it (such a wave has
 // lost already). In a resolve launch of its own bx/by are pre-batch:
 // mv_from equals what they give and the bounds test never fires.
-template <class Claims> __device__ __forceinline__
+template <class Claims, class Counters> __device__ __forceinline__
 bool resolve_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
-                  const int32_t* mv_from, int i, const Move& mv) {
+                  const Counters& cnt, const int32_t* mv_from, int i,
+                  const Move& mv) {
   const int lane = threadIdx.x & 63;
   bool bad = false;
   if (mv.is_macro()) {
@@ -719,8 +751,8 @@ bool resolve_move(const PlaceDev& p, const MovesDev& m, const Claims& c,
   }
   const bool win = !__any(bad);
   if (lane == 0) {
-    if (!win) { m.mv_flags[i] = 0; atomicAdd(&m.counters[3], 1); }
-    else { m.mv_flags[i] = 2; atomicAdd(&m.counters[2], 1); }
+    if (!win) { m.mv_flags[i] = 0; cnt.add(CNT_CONFLICTS); }
+    else { m.mv_flags[i] = 2; cnt.add(CNT_WINNERS); }
   }
   return win;
 }
@@ -737,10 +769,12 @@ void refresh_net(const PlaceDev& p, int32_t n, const Pos& pos,
 // MV_RECOMPUTE, recompute them with the hypothetical positions over the
 // PRE-move state (so lanes never read positions another lane just wrote;
 // duplicate refreshes of nets shared by both blocks are idempotent). Both
-// give the same words. Then lane 0 commits grid and positions.
+// give the same words. Then lane 0 commits grid and positions. The cost
+// totals are not kept up here: place_refresh_costs_kernel recomputes them
+// from the cached net costs whenever the host wants them.
 __device__ __forceinline__
 void apply_move(const PlaceDev& p, const MovesDev& m, int i, const Move& mv,
-                float timing_tradeoff, double* cost_acc /*[2]: dbb, dtd*/) {
+                float timing_tradeoff) {
   const int lane = threadIdx.x & 63;
   if (mv.is_macro()) {
     const MacroPos ms = mv.macro();
@@ -794,10 +828,6 @@ void apply_move(const PlaceDev& p, const MovesDev& m, int i, const Move& mv,
       if (other >= 0) { p.bx[other] = x0; p.by[other] = y0; p.bslot[other] = s0; }
     }
   }
-  if (lane == 0) {
-    unsafeAtomicAdd(&cost_acc[0], (double)m.mv_dbb[i]);
-    unsafeAtomicAdd(&cost_acc[1], (double)m.mv_dtd[i]);
-  }
 }
 
 // ---- pnr_place_batch: reset, propose, resolve, apply ---------------
@@ -817,7 +847,8 @@ __global__ void place_propose_kernel(PlaceDev p, MovesDev m, int32_t* mv_from,
                                      Sched s) {
   const int i = move_index();
   if (i >= m.n_moves) return;
-  propose_move(p, m, MinClaims{m.net_claim, m.loc_claim, i}, mv_from, i, s);
+  propose_move(p, m, MinClaims{m.net_claim, m.loc_claim, i},
+               DirectCounters{m.counters}, mv_from, i, s);
 }
 
 __launch_bounds__(64 * PROP_WAVES, 2)
@@ -825,29 +856,40 @@ __global__ void place_resolve_kernel(PlaceDev p, MovesDev m,
                                      const int32_t* mv_from) {
   const int i = move_index();
   if (i >= m.n_moves || m.mv_flags[i] != 1) return;
-  resolve_move(p, m, MinClaims{m.net_claim, m.loc_claim, i}, mv_from, i,
-               Move(m, i));
+  resolve_move(p, m, MinClaims{m.net_claim, m.loc_claim, i},
+               DirectCounters{m.counters}, mv_from, i, Move(m, i));
 }
 
 __launch_bounds__(64 * PROP_WAVES, 2)
 __global__ void place_apply_kernel(PlaceDev p, MovesDev m,
-                                   float timing_tradeoff, double* cost_acc) {
+                                   float timing_tradeoff) {
   const int i = move_index();
   if (i >= m.n_moves || m.mv_flags[i] != 2) return;
-  apply_move(p, m, i, Move(m, i), timing_tradeoff, cost_acc);
+  apply_move(p, m, i, Move(m, i), timing_tradeoff);
 }
 
 // ---- pnr_place_run: propose, commit --------------------------------
 // Two launches per batch, no reset, no host round trip per batch.
-// Control block ctrl[4] (device, zeroed by the host per run_batches call):
-//   [0] done     set by the stop rule; every kernel returns at once on it
-//   [1] n_exec   batches executed so far in this run_batches call
-//   [2] ticket   workgroup arrival counter of a checking commit launch
+// Device state of a run_batches call, zeroed by the host at its start:
+//   ctrl     [0] done    set by the stop rule; every kernel returns at
+//                        once on it. Read first thing by every wave.
+//            [1] n_exec  batches executed so far in this run_batches call
+//            [2] ticket  workgroup arrival counter of a checking commit
+//                        launch
+//            In the host's buffer ctrl follows the totals m.counters[0..3]
+//            in one 128-byte line. The counter atomics of every wave go to
+//            the shards and not to this line; the only atomics it still
+//            takes are the tickets, one per workgroup at the end of every
+//            fourth commit launch. A line of its own for the ticket was
+//            measured and changed nothing (docs/MEASUREMENTS.md).
+//   shards   n_shards lines of counters (see ShardCounters)
 struct RunDev {
   int32_t* mv_from;                  // proposer's source tile x*gy+y
   unsigned long long* net_claim;     // [num_nets] EpochClaims words
   unsigned long long* loc_claim;     // [gx*gy]
   int32_t* ctrl;
+  int32_t* shards;                   // [n_shards * SHARD_WORDS]
+  int32_t n_shards;                  // a power of two
 };
 
 __launch_bounds__(64 * PROP_WAVES, 2)
@@ -857,52 +899,73 @@ __global__ void place_propose_run_kernel(PlaceDev p, MovesDev m, RunDev r,
   const int i = move_index();
   if (i >= m.n_moves) return;
   const EpochClaims c{r.net_claim, r.loc_claim, claim_key(s.batch, i)};
-  propose_move(p, m, c, r.mv_from, i, s);
+  propose_move(p, m, c, ShardCounters(r.shards, r.n_shards - 1), r.mv_from, i,
+               s);
 }
 
 // Resolve and apply of one move by its wave: a winner applies at once,
 // while other waves are still deciding (see resolve_move).
 __device__ __forceinline__
 void commit_move(const PlaceDev& p, const MovesDev& m, const RunDev& r,
-                 float timing_tradeoff, double* cost_acc, uint32_t batch) {
+                 float timing_tradeoff, uint32_t batch) {
   const int i = move_index();
   if (i >= m.n_moves || m.mv_flags[i] != 1) return;
   const Move mv(m, i);
   const EpochClaims c{r.net_claim, r.loc_claim, claim_key(batch, i)};
-  if (resolve_move(p, m, c, r.mv_from, i, mv))
-    apply_move(p, m, i, mv, timing_tradeoff, cost_acc);
+  if (resolve_move(p, m, c, ShardCounters(r.shards, r.n_shards - 1),
+                   r.mv_from, i, mv))
+    apply_move(p, m, i, mv, timing_tradeoff);
 }
 
-// check != 0 on the 4th, 8th, ... batch of a run_batches call: the last
-// workgroup to arrive (ticket == gridDim.x - 1) evaluates the stop rule.
+__device__ __forceinline__ int wave_sum_i32(int v) {
+  for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
+  return v;
+}
+
+// check != 0 on the 4th, 8th, ... batch of a run_batches call: the first
+// wave of the last workgroup to arrive (ticket == gridDim.x - 1) folds the
+// counter shards into m.counters and evaluates the stop rule on the totals.
 // Nothing waits: every workgroup adds its ticket and leaves.
 __launch_bounds__(64 * PROP_WAVES, 2)
 __global__ void place_commit_kernel(PlaceDev p, MovesDev m, RunDev r,
-                                    float timing_tradeoff, double* cost_acc,
-                                    uint32_t batch, int check,
-                                    int32_t target_moves) {
+                                    float timing_tradeoff, uint32_t batch,
+                                    int check, int32_t target_moves) {
   if (r.ctrl[0]) return;
-  commit_move(p, m, r, timing_tradeoff, cost_acc, batch);
+  commit_move(p, m, r, timing_tradeoff, batch);
   if (!check) return;
   // this wave's counter atomics have been performed ...
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x != 0) return;
+  if (threadIdx.x >= 64) return;
+  const int lane = threadIdx.x;
   // ... and are ordered before the ticket
   __threadfence();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  int ticket = __hip_atomic_fetch_add(&r.ctrl[2], 1, __ATOMIC_RELAXED,
-                                      __HIP_MEMORY_SCOPE_AGENT);
-  if (ticket != (int)gridDim.x - 1) return;
+  int ticket = 0;
+  if (lane == 0)
+    ticket = __hip_atomic_fetch_add(&r.ctrl[2], 1, __ATOMIC_RELAXED,
+                                    __HIP_MEMORY_SCOPE_AGENT);
+  if (__shfl(ticket, 0) != (int)gridDim.x - 1) return;
   __threadfence();
-  int att = __hip_atomic_load(&m.counters[0], __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-  int acc = __hip_atomic_load(&m.counters[1], __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
-  int win = __hip_atomic_load(&m.counters[2], __ATOMIC_RELAXED,
-                              __HIP_MEMORY_SCOPE_AGENT);
+  // The fold may trust the shards. Every workgroup of this launch performed
+  // its commit-side adds before it took its ticket (waitcnt, barrier,
+  // fence, ticket, above), and this wave holds the last ticket; the adds of
+  // this batch's propose launch, and of every earlier batch, were complete
+  // at a kernel boundary. Launches that returned on `done` added nothing.
+  // The loads are agent-scope atomics, so they are served by L2, where the
+  // adds were performed, and not by a stale line of this CU's L1.
+  int tot[4] = {0, 0, 0, 0};
+  for (int sh = lane; sh < r.n_shards; sh += 64)
+    for (int k = 0; k < 4; ++k)
+      tot[k] += __hip_atomic_load(&r.shards[(int64_t)sh * SHARD_WORDS + k],
+                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int k = 0; k < 4; ++k) tot[k] = wave_sum_i32(tot[k]);
+  if (lane != 0) return;
+  for (int k = 0; k < 4; ++k) m.counters[k] = tot[k];
   r.ctrl[1] += 4;
-  if (win + (att - acc) >= target_moves) r.ctrl[0] = 1;
+  if (tot[CNT_WINNERS] + (tot[CNT_ATTEMPTS] - tot[CNT_ACCEPTED]) >=
+      target_moves)
+    r.ctrl[0] = 1;
   __hip_atomic_store(&r.ctrl[2], 0, __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -958,6 +1021,10 @@ struct PlaceLaunchArgs {
   int32_t* mv_from;
   unsigned long long* net_claim64; unsigned long long* loc_claim64;
   int32_t* run_ctrl;
+  // the counter shards, n_shards lines of 128 bytes (see RunDev),
+  // 128-byte aligned
+  int32_t* run_shards;
+  int32_t n_shards;
   // stored costs of accepted moves (see MovesDev)
   float* mv_ncost; float* mv_ntcost;
   int32_t cost_k;
@@ -1016,7 +1083,7 @@ int pnr_place_batch(const PlaceLaunchArgs* a, void* stream) {
   hipLaunchKernelGGL(place_resolve_kernel, dim3(mg), dim3(64 * PROP_WAVES),
                      0, s, p, m, (const int32_t*)a->mv_from);
   hipLaunchKernelGGL(place_apply_kernel, dim3(mg), dim3(64 * PROP_WAVES),
-                     0, s, p, m, a->timing_tradeoff, a->cost_acc);
+                     0, s, p, m, a->timing_tradeoff);
   return (int)hipGetLastError();
 }
 
@@ -1030,7 +1097,8 @@ int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
                   int32_t target_moves, int32_t n_batches, void* stream) {
   if (n_batches < 0 || (n_batches & 3) || first_batch == 0 ||
       !batch_args_ok(a) || !a->net_claim64 || !a->loc_claim64 ||
-      !a->run_ctrl)
+      !a->run_ctrl || !a->run_shards || a->n_shards < 1 ||
+      (a->n_shards & (a->n_shards - 1)) || ((uintptr_t)a->run_shards & 127))
     return (int)hipErrorInvalidValue;
   PlaceDev p; MovesDev m;
   unpack(a, p, m);
@@ -1038,6 +1106,8 @@ int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
   r.mv_from = a->mv_from;
   r.net_claim = a->net_claim64; r.loc_claim = a->loc_claim64;
   r.ctrl = a->run_ctrl;
+  r.shards = a->run_shards;
+  r.n_shards = a->n_shards;
   hipStream_t s = (hipStream_t)stream;
   int mg = (m.n_moves + PROP_WAVES - 1) / PROP_WAVES;
   for (int32_t k = 0; k < n_batches; ++k) {
@@ -1045,7 +1115,7 @@ int pnr_place_run(const PlaceLaunchArgs* a, uint32_t first_batch,
     hipLaunchKernelGGL(place_propose_run_kernel, dim3(mg),
                        dim3(64 * PROP_WAVES), 0, s, p, m, r, sched(a, batch));
     hipLaunchKernelGGL(place_commit_kernel, dim3(mg), dim3(64 * PROP_WAVES),
-                       0, s, p, m, r, a->timing_tradeoff, a->cost_acc, batch,
+                       0, s, p, m, r, a->timing_tradeoff, batch,
                        (int)(((k + 1) & 3) == 0), target_moves);
   }
   return (int)hipGetLastError();

@@ -53,6 +53,8 @@ class PlaceLaunchArgs(ct.Structure):
         ("mv_from", ct.c_void_p),
         ("net_claim64", ct.c_void_p), ("loc_claim64", ct.c_void_p),
         ("run_ctrl", ct.c_void_p),
+        # the counter shards (128-byte lines)
+        ("run_shards", ct.c_void_p), ("n_shards", ct.c_int32),
         # stored costs of accepted moves, [n_moves x cost_k] each
         ("mv_ncost", ct.c_void_p), ("mv_ntcost", ct.c_void_p),
         ("cost_k", ct.c_int32),
@@ -63,6 +65,20 @@ class PlaceLaunchArgs(ct.Structure):
 # period). Between chunks the host reads the control block once; past the
 # stop point the rest of a chunk costs empty launches only.
 RUN_CHUNK_BATCHES = 32
+
+# The run loop's device state is one int32 buffer of 128-byte lines:
+#   line 0       counters[0..3] (the totals; in the run loop written by the
+#                stop rule's fold only), then the control block: done,
+#                batches executed, ticket. The first RUN_HOST_WORDS words
+#                are all the host reads.
+#   lines 1...   COUNTER_SHARDS lines, four counters at the start of each:
+#                what the waves' counter atomics target
+LINE_WORDS = 32
+RUN_HOST_WORDS = 8
+# Shards the run loop spreads its counter atomics over (a power of two).
+# With 64 a line takes the atomics of about 9 of bitcoin_miner's 588
+# workgroups; docs/MEASUREMENTS.md has the sweep (8, 64, 1024).
+COUNTER_SHARDS = 64
 
 
 def _lib():
@@ -239,11 +255,16 @@ class GpuPlacer:
                                       device=device)
         self.t_mv_ntcost = torch.zeros(nm * self.cost_k, dtype=torch.float32,
                                        device=device)
-        # counters [4] and the run loop's control block [4] (done, batches
-        # executed, ticket, unused) share one buffer: one copy reads both
-        self.t_run_state = torch.zeros(8, dtype=torch.int32, device=device)
+        # counters, control block and counter shards share one buffer
+        # (layout: LINE_WORDS above): one zero_() clears them all
+        self.n_shards = COUNTER_SHARDS
+        self.t_run_state = torch.zeros((1 + self.n_shards) * LINE_WORDS,
+                                       dtype=torch.int32, device=device)
+        if self.t_run_state.data_ptr() % (4 * LINE_WORDS):
+            raise RuntimeError("run state is not 128-byte aligned")
         self.t_counters = self.t_run_state[:4]
-        self.t_run_ctrl = self.t_run_state[4:]
+        self.t_run_ctrl = self.t_run_state[4:RUN_HOST_WORDS]
+        self.t_run_shards = self.t_run_state[LINE_WORDS:]
         self.t_cost_acc = torch.zeros(2, dtype=torch.float64, device=device)
 
         self.lib = _lib()
@@ -404,6 +425,8 @@ class GpuPlacer:
             a.loc_claim64 = ptr(self.t_loc_claim64)
         a.mv_from = ptr(self.t_mv_from)
         a.run_ctrl = ptr(self.t_run_ctrl)
+        a.run_shards = ptr(self.t_run_shards)
+        a.n_shards = self.n_shards
         a.mv_ncost = ptr(self.t_mv_ncost); a.mv_ntcost = ptr(self.t_mv_ntcost)
         a.cost_k = self.cost_k
         a.counters = ptr(self.t_counters); a.n_moves = self.n_moves
@@ -439,7 +462,7 @@ class GpuPlacer:
         if self.legacy_batches:
             return self._run_batches_legacy(T, rlim, target_moves, tt,
                                             bb_norm, td_norm, max_batches)
-        self.t_run_state.zero_()    # counters and control block
+        self.t_run_state.zero_()    # counters, control block, shards
         a = self._args(T=T, rlim=rlim, tt=tt,
                        inv_bb=1.0 / bb_norm, inv_td=1.0 / td_norm)
         target = int(min(max(math.ceil(target_moves), -0x7FFFFFFF),
@@ -455,7 +478,7 @@ class GpuPlacer:
             hip_api.check(rc, "place_run")
             enq += n
             # one small device-to-host copy per chunk (it synchronises)
-            st = self.t_run_state.cpu().numpy()
+            st = self.t_run_state[:RUN_HOST_WORDS].cpu().numpy()
             att, acc = int(st[0]), int(st[1])
             done, executed = int(st[4]), int(st[5])
             if done:
